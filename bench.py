@@ -5,6 +5,10 @@
       N > 1 without WORLD_SIZE in the environment: the script re-launches itself under torch.distributed.run with N
       ranks on 127.0.0.1 (one rank per GPU; fails loudly when the node has fewer than N devices).  Under a launcher
       (WORLD_SIZE set) --gpus must equal WORLD_SIZE.
+  --dump-outputs DIR: after the K timed steps, what the last one handed its caller (kept rows, global indices,
+      per-frame budgets; cfg5: per clip) goes to DIR/<name>.npy as float32 / float64, 64 MB at most in all (larger rows
+      arrays: a fixed seeded sample of rows, numbers in <name>_sample_rows.npy).  Inputs are seeded: the same arguments
+      give the same inputs on every run, so two builds can be compared output for output.
 
 A "step" = one whole pass over one batch of synthetic frame-token embeddings already resident in
 HBM: channel selection, scoring, budgets, per-frame selection and the kept-row gather
@@ -65,6 +69,7 @@ WORKLOADS = {
     "cfg5": (128, 196, 4096, torch.float16, 0.25),        # per CLIP; the workload is 16 of them, 16 / world per rank
 }
 CFG5_CLIPS = 16
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all (every rank together)
 DT_NAME = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32"}
 
 
@@ -99,6 +104,38 @@ def pmc_traffic(kernel, workload, world):
         if d.get("workload", "").startswith(workload + ":") and kernel in d.get("kernels", {}):
             return d["kernels"][kernel]["hbm_bytes"]
     return None
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: write `arrays` (name -> tensor, what the timed path hands its caller) as path/<name>.npy, floating
+    point as float32 and integers as float64 (exact below 2**53).  When they exceed `budget` bytes, every 2-D array is
+    cut to a fixed, seeded sample of its rows, stored beside it as <name>_sample_rows.npy (row numbers, float64)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t.to(torch.float32 if t.is_floating_point() else torch.float64)
+    nbytes = lambda a: a.numel() * a.element_size()      # noqa: E731
+    total = sum(nbytes(a) for a in host.values())
+    if total > budget:
+        big = [n for n, a in host.items() if a.dim() == 2 and a.shape[0] > 1]
+        small = total - sum(nbytes(host[n]) for n in big)
+        # (less the sample-row files at their largest and 4 KiB per .npy header)
+        room = budget - small - sum(8 * host[n].shape[0] for n in big) - 4096 * (len(host) + len(big))
+        big_total = sum(nbytes(host[n]) for n in big)
+        if room <= 0 or not big:
+            raise SystemExit(f"[bench] --dump-outputs: {total} bytes of outputs do not fit {budget}")
+        for n in big:
+            a = host[n]
+            keep = max(1, min(a.shape[0], int(a.shape[0] * room / big_total)))
+            g = torch.Generator().manual_seed(0)
+            rows = torch.randperm(a.shape[0], generator=g)[:keep].sort().values
+            host[n] = a[rows]
+            host[n + "_sample_rows"] = rows.to(torch.float64)
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+    print(f"[bench] wrote {len(host)} output arrays to {path}", file=sys.stderr, flush=True)
 
 
 def time_steps(fn, steps, dist_on):
@@ -266,11 +303,18 @@ def bench_replicas(args, rank, world, dev, vc, _ffi, synth):
         ref = oracle.compress_indices(clips[0].cpu(), N, base)
         if res0.ks.cpu().tolist() != ref["ks"].tolist() or not torch.equal(res0.global_idx.cpu(), ref["global_idx"]):
             raise SystemExit("[bench] PARITY FAILURE (cfg5 clip 0): kept indices / budgets differ from the oracle")
-    step = lambda: vc.vidcom2.compress_batch(clips, N, base)      # noqa: E731
+    last = []
+    step = lambda: last.__setitem__(slice(None), vc.vidcom2.compress_batch(clips, N, base))      # noqa: E731
     for _ in range(args.warmup):
         step()
     dist_on = world > 1
     elapsed = time_steps(step, args.steps, dist_on)
+    if args.dump_outputs:                              # (clip numbers over the whole workload: rank r holds r*mine ...)
+        got = {}
+        for i, r in enumerate(last):
+            got.update({f"clip{rank * mine + i:02d}_{k}": v for k, v in
+                        (("rows", r.rows), ("global_idx", r.global_idx), ("ks", r.ks)) if v is not None})
+        dump_outputs(args.dump_outputs, got, DUMP_BYTES // world)
     if dist_on:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
@@ -303,7 +347,11 @@ def main():
     ap.add_argument("--workload", default="target", choices=sorted(WORKLOADS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (every rank: _rank<r> suffixes)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("[bench] --steps must be >= 1")
     if os.environ.get("VC2_BENCH_WATCHDOG"):
         # a run that is still going after this many seconds dumps every thread's Python stack to stderr and exits (the
         # test-suite's subprocess runs set it: a hung rank says where instead of sitting out a 30-minute collective timeout)
@@ -403,6 +451,13 @@ def main():
     for _ in range(args.warmup):
         step()
     elapsed = time_steps(step, args.steps, dist_on)
+    if args.dump_outputs:
+        last = finish()                                # (the plan's outputs: written by the last timed step)
+        sfx = f"_rank{rank}" if world > 1 else ""
+        got = {"rows": last.rows, "global_idx": last.global_idx, "ks": last.ks}
+        if dist_on:
+            got["local_idx"] = last.local_idx
+        dump_outputs(args.dump_outputs, {k + sfx: v for k, v in got.items() if v is not None}, DUMP_BYTES // world)
     if dist_on:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)

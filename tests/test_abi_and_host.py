@@ -144,6 +144,36 @@ def test_bench_issues_a_constant_number_of_passes_per_rank_before_timing():
     assert bench.warm_clocks(lambda: n.__setitem__(0, n[0] + 1), False, sync=lambda: None, seconds=0.01) == n[0] >= 10
 
 
+def test_bench_dump_outputs_fits_its_budget_and_repeats(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 files, at most the budget in all (rows arrays beyond it cut to a seeded
+    sample of rows whose numbers are stored beside them), and the same files for the same outputs."""
+    import glob
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("vc2_bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(1)
+    K, D, budget = 3000, 512, 2_000_000
+    rows = torch.randn(K, D, generator=g).to(torch.bfloat16)
+    arrays = {"rows": rows, "global_idx": torch.arange(K) * 3 + 1, "ks": torch.full((16,), K // 16)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays, budget)
+    files = sorted(glob.glob(str(tmp_path / "a" / "*.npy")))
+    assert sorted(os.path.basename(f) for f in files) == ["global_idx.npy", "ks.npy", "rows.npy", "rows_sample_rows.npy"]
+    assert sum(os.path.getsize(f) for f in files) <= budget
+    for f in files:
+        assert np.array_equal(np.load(f), np.load(f.replace(os.sep + "a" + os.sep, os.sep + "b" + os.sep)))
+    got, pick = np.load(str(tmp_path / "a" / "rows.npy")), np.load(str(tmp_path / "a" / "rows_sample_rows.npy"))
+    assert got.dtype == np.float32 and pick.dtype == np.float64 and 0 < len(pick) < K
+    assert np.array_equal(got, rows.float().numpy()[pick.astype(np.int64)])
+    assert np.load(str(tmp_path / "a" / "global_idx.npy")).dtype == np.float64
+    # under the budget: everything, whole
+    bench.dump_outputs(str(tmp_path / "c"), arrays, 64_000_000)
+    assert np.array_equal(np.load(str(tmp_path / "c" / "rows.npy")), rows.float().numpy())
+    assert not os.path.exists(str(tmp_path / "c" / "rows_sample_rows.npy"))
+
+
 def test_f16_fast_quotient_is_the_ieee_quotient(tmp_path):
     """The fp16 fast path of sweep 2 (k_norm_colsum2) divides by q = fma(e, r, q0), q0 = x r, e = fma(-dn, q0, x): the
     exhaustive checker behind it (tests/tools/check_f16_quotient.c; every fp16 x, a strided subset of the denominators
