@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round profile set on the GPU box: scripts/r2_profile.sh <tag>   -> gpurun_out/<tag>/...
+# Profile set on the GPU box: scripts/profile_set.sh <tag>   (one directory <tag>/ of traces, counters and a bench line)
 set -u
 tag=$1
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag

@@ -780,7 +780,7 @@ def test_a_guard_hit_of_any_frame_reaches_the_caller():
                          ids=lambda s_: "x".join(map(str, s_)))
 def test_selection_engines_and_launch_forms_agree(shape):
     """Round 6 changed HOW the channel selection runs, not what it computes: thread-contiguous register rounds
-    (k_chan_select4 / sel4_round; VC2_SEL4=0: the 16-wave LDS rounds of rounds 3-5; VC2_SEL3=1: the ballot form) and the
+    (k_chan_select4 / sel4_round; VC2_SEL4=0: the 16-wave LDS rounds of rounds 3-5) and the
     variance reduction + selection in ONE launch with polled variances (k_var_select; VC2_VARSEL=0: two launches).  Every
     form must give the same channel order, scores, budgets and kept indices -- and the oracle's."""
     import os
@@ -789,11 +789,11 @@ def test_selection_engines_and_launch_forms_agree(shape):
     O.set_mode("torch")
     ref = O.compress_indices(x, N, 0.25)
     xd = x.to(dev())
-    keys = ("VC2_SEL4", "VC2_VARSEL", "VC2_SEL3")
+    keys = ("VC2_SEL4", "VC2_VARSEL")
     old = {k: os.environ.get(k) for k in keys}
     outs = []
     try:
-        for form in ({}, {"VC2_VARSEL": "0"}, {"VC2_SEL4": "0"}, {"VC2_SEL3": "1"}):
+        for form in ({}, {"VC2_VARSEL": "0"}, {"VC2_SEL4": "0"}):
             for k in keys:
                 os.environ.pop(k, None)
             os.environ.update(form)

@@ -297,38 +297,30 @@ def test_bench_two_rank_code_path_on_one_gpu():
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["value"] > 0 and d["config"]["parallelism"] == "frame-shard x2"
 
 
-def _run_bounded(cmd, env, cwd, timeout=420, attempts=2):
+def _run_bounded(cmd, env, cwd, timeout=420):
     """subprocess.run for the multi-process bench runs, bounded: its own session (a timeout kills the launcher AND its
-    ranks -- an orphaned rank would keep the pipes open and block communicate() for good), bench.py's watchdog (every
-    thread's Python stack on stderr when a rank is still going after timeout - 120 s), and ONE more attempt when a run was
-    cut off that way.  (Written for an intermittent hang of the two-rank runs -- 3 of 22 loops over this file -- that the
-    watchdog's stacks then pinned on bench.py itself: its clock-warming loop was bounded by each rank's OWN clock, so now
-    and then one rank ran ten passes, i.e. forty all-gathers, more than the other.  Fixed there; the bounds stay.)
-    An ordinary failure is returned as is."""
+    ranks -- an orphaned rank would keep the pipes open and block communicate() for good) and bench.py's watchdog (every
+    thread's Python stack on stderr when a rank is still going after timeout - 120 s).  A run cut off either way fails
+    the test with the stderr it collected; an ordinary failure is returned as is."""
     import signal
     import subprocess
-    import warnings
     env = dict(env, VC2_BENCH_WATCHDOG=str(max(60, timeout - 120)))
-    last = None
-    for attempt in range(attempts):
-        p = subprocess.Popen(cmd, env=env, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
-                             start_new_session=True)
+    p = subprocess.Popen(cmd, env=env, cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
+                         start_new_session=True)
+    try:
+        out, err = p.communicate(timeout=timeout)
+        cut = p.returncode != 0 and "Timeout (" in err                  # (faulthandler's watchdog header)
+    except subprocess.TimeoutExpired:
         try:
-            out, err = p.communicate(timeout=timeout)
-            cut = p.returncode != 0 and "Timeout (" in err              # (faulthandler's watchdog header)
-        except subprocess.TimeoutExpired:
-            try:
-                os.killpg(p.pid, signal.SIGKILL)
-            except ProcessLookupError:
-                pass
-            out, err = p.communicate()
-            err = f"[cut off after {timeout} s]\n" + err
-            cut = True
-        last = subprocess.CompletedProcess(cmd, p.returncode if p.returncode is not None else -9, out, err)
-        if not cut:
-            return last
-        warnings.warn(f"bench subprocess attempt {attempt + 1} was cut off by its watchdog / timeout:\n{err[-3000:]}")
-    return last
+            os.killpg(p.pid, signal.SIGKILL)
+        except ProcessLookupError:
+            pass
+        out, err = p.communicate()
+        err = f"[cut off after {timeout} s]\n" + err
+        cut = True
+    if cut:
+        pytest.fail(f"bench subprocess was cut off by its watchdog / timeout:\n{err[-3000:]}")
+    return subprocess.CompletedProcess(cmd, p.returncode, out, err)
 
 
 def _run_bench(args, env_extra=None, timeout=600):

@@ -41,13 +41,6 @@
 
 #include "vc2_device.h"
 
-#ifndef VC2_PROBE_D3
-#define VC2_PROBE_D3 0
-#endif
-#ifndef VC2_PROBE_S2
-#define VC2_PROBE_S2 0
-#endif
-
 using namespace vc2;
 
 #ifdef VC2_DEBUG_TIMING
@@ -95,9 +88,6 @@ inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 // VEC columns, K = x[0][c] (a shift: constant columns give exactly 0 and the final subtraction
 // is well conditioned).  The 4 waves combine through LDS; one partial per (row group, column).
 constexpr int kStatsWaves = 4;
-#ifndef VC2_S1_PROBE
-#define VC2_S1_PROBE 0
-#endif
 
 // Row groups are CANONICAL: a group is one of `splits` pieces of one frame, the shift K of a group
 // is the first row of its STAT BLOCK (kStatBlockFrames frames), and the groups of a block are added in a fixed order
@@ -230,30 +220,11 @@ __global__ __launch_bounds__(kStatsWaves * 64) void k_chan_stats(const void* __r
     } else
     for (int64_t r = r0 + wave; r < r1; r += int64_t(kStatsWaves) * U) {
       RawVec<DT, VEC> raw[U];
-#if VC2_S1_PROBE == 2      // (timing probe, results invalid: the arithmetic alone -- one round of loads, reused)
-      if (r == r0 + wave) {
-#endif
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t rr = r + int64_t(u) * kStatsWaves;
         raw[u] = rr < r1 ? load_raw<DT, VEC>(x, rr * D + int64_t(cv) * VEC) : zero_raw<DT, VEC>();
       }
-#if VC2_S1_PROBE == 2
-      }
-      if constexpr (VEC == 8) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) asm volatile("" : "+v"(raw[u].v.x), "+v"(raw[u].v.y), "+v"(raw[u].v.z), "+v"(raw[u].v.w));
-      }
-#endif
-#if VC2_S1_PROBE == 1      // (timing probe, results invalid: the loads alone)
-      if constexpr (VEC == 8) {
-        unsigned acc = 0;
-#pragma unroll
-        for (int u = 0; u < U; ++u) acc ^= raw[u].v.x ^ raw[u].v.y ^ raw[u].v.z ^ raw[u].v.w;
-        s[0] += double(acc);
-      }
-      continue;
-#endif
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int64_t rr = r + int64_t(u) * kStatsWaves;
@@ -431,16 +402,10 @@ __global__ __launch_bounds__(CW * kRedGL) void k_var_from_stats(const double* __
 // piece of work, chan_order_body, done by several workgroups side by side (slices of the sorted order, see
 // introsort2): either its own kernel, or RIDER workgroups of sweep 2 (k_norm_colsum) -- its consumers run after
 // the sweep.
-#ifndef VC2_SEL_NT
-#define VC2_SEL_NT 1024
-#endif
-constexpr int kSelNT = VC2_SEL_NT;  // k_chan_select
-#ifndef VC2_SEL_ACTIVE
-#define VC2_SEL_ACTIVE 16
-#endif
+constexpr int kSelNT = 1024;  // k_chan_select
 // waves that take part in a cooperative round (the rest idle at the barriers).  Measured at D = 3584: 16 -> 20.8 us,
 // 8 -> 22.2, 4 -> 27.4: the elements per thread cost more than the extra waves per SIMD
-constexpr int kSelActive = VC2_SEL_ACTIVE;
+constexpr int kSelActive = 16;
 constexpr int kSelCoop = 8192 / (64 * kSelActive * 4);                      // quads per thread at D = 8192
 constexpr int kSelSolo = kSelActive >= 16 ? 2 : 4;
 constexpr int kOrdNT = 256;         // k_chan_order: 4 waves per slice, like the rider workgroups of sweep 2
@@ -559,15 +524,14 @@ __device__ __forceinline__ void chan_select_epilogue_bitmap(const Sel2<uint32_t>
   if (tid == 0) VC2_ROUND(S, 299, k);
 }
 
-// the LDS-round engine (vc2_select2.h, second generation) on NT threads: every D <= 8192, both word widths
-template <typename W, int NT, int NPRE>
-__device__ __forceinline__ void chan_select_body(unsigned char* smem, const float (&pre)[NPRE], int D, int k,
+// the LDS-round engine (vc2_select2.h, second generation) on kSelNT threads: every D <= 8192, both word widths
+template <typename W>
+__device__ __forceinline__ void chan_select_body(unsigned char* smem, const float (&pre)[kSelPre], int D, int k,
                                                  uint8_t* __restrict__ mask, int* __restrict__ cols,
                                                  int* __restrict__ perm, uint32_t* __restrict__ wperm,
                                                  uint32_t* __restrict__ wcpos, int* status) {
   using T = WordTr<W>;
-  constexpr int NW = NT / 64;
-  constexpr int SOLO = NT == kSelNT ? kSelSolo : 4, COOP = NT == kSelNT ? kSelCoop : 8, ACT = NT == kSelNT ? kSelActive : NW;
+  constexpr int NW = kSelNT / 64;
   const int tid = threadIdx.x;
   Sel2<W> S = sel2_carve<W>(smem, D, status);
 #if defined(VC2_DEBUG_TIMING)
@@ -575,13 +539,13 @@ __device__ __forceinline__ void chan_select_body(unsigned char* smem, const floa
 #endif
   if (tid == 0) VC2_ROUND(S, 201, D);                             // the variances are in registers
 #pragma unroll
-  for (int j = 0; j < NPRE; ++j) { const int i = tid + j * NT; if (i < D) S.w[i] = T::pack(topk_key(pre[j]), i); }
+  for (int j = 0; j < kSelPre; ++j) { const int i = tid + j * kSelNT; if (i < D) S.w[i] = T::pack(topk_key(pre[j]), i); }
   __syncthreads();
   if (tid == 0) VC2_ROUND(S, 202, D);                             // packed words in LDS
-  if (k >= D) { if (perm) introselect2<W, NW, SOLO, COOP, ACT>(S, D, D - 1, tid); }    // nth_element(n-1) still permutes
-  else topk_smallest2<W, NW, SOLO, COOP, ACT>(S, D, k, tid);
+  if (k >= D) { if (perm) introselect2<W, NW, kSelSolo, kSelCoop, kSelActive>(S, D, D - 1, tid); }    // nth_element(n-1) still permutes
+  else topk_smallest2<W, NW, kSelSolo, kSelCoop, kSelActive>(S, D, k, tid);
   // (no barrier here: both replays end with one, and the cases that replay nothing have the barrier above behind them)
-  chan_select_epilogue<W, NT>(S, D, k, mask, cols, perm, wperm, wcpos);
+  chan_select_epilogue<W, kSelNT>(S, D, k, mask, cols, perm, wperm, wcpos);
 }
 
 #ifndef VC2_DEV_ONLY
@@ -600,8 +564,8 @@ __global__ __launch_bounds__(kSelNT) void k_chan_select(const float* __restrict_
   for (int j = 0; j < kSelPre; ++j) bad |= key_fits_u32(pre[j]) ? 0 : 1;
   // widened 16-bit variances pack into 32-bit words (the common case); arbitrary fp32 ones take 64-bit words
   // (wperm / wcpos are only requested for 16-bit inputs)
-  if (__syncthreads_or(bad)) chan_select_body<uint64_t, kSelNT, kSelPre>(smem, pre, D, k, mask, cols, perm, nullptr, nullptr, status);
-  else chan_select_body<uint32_t, kSelNT, kSelPre>(smem, pre, D, k, mask, cols, perm, wperm, wcpos, status);
+  if (__syncthreads_or(bad)) chan_select_body<uint64_t>(smem, pre, D, k, mask, cols, perm, nullptr, nullptr, status);
+  else chan_select_body<uint32_t>(smem, pre, D, k, mask, cols, perm, wperm, wcpos, status);
   if (threadIdx.x == 0) VC2_STAMP(209);
 }
 #endif
@@ -657,7 +621,7 @@ __device__ __forceinline__ void chan_select4_body(unsigned char* smem, const flo
     float pre[kSelPre];                                  // (POLL: every thread has seen its own words, the barrier has passed: all are there)
 #pragma unroll
     for (int j = 0; j < kSelPre; ++j) { const int i = tid + j * kSelNT; pre[j] = var_f32[i < D ? i : D - 1]; }
-    chan_select_body<uint64_t, kSelNT, kSelPre>(smem, pre, D, k, mask, cols, perm, nullptr, nullptr, status);
+    chan_select_body<uint64_t>(smem, pre, D, k, mask, cols, perm, nullptr, nullptr, status);
     if (tid == 0) VC2_STAMP(209);
     return;
   }
@@ -701,6 +665,7 @@ struct VarSelArgs {
   int k; int* cols; int* perm; uint32_t* wperm; uint32_t* wcpos; int* status;
   int warm;      // bytes of this kernel's own code the selection workgroup reads (as data) while it waits: see k_var_select
 };
+constexpr int kCodeWarmBytes = 88 * 1024;      // VarSelArgs::warm (less than k_var_select's code: the read stays inside it)
 template <int DT>
 __global__ __launch_bounds__(kSelNT) void k_var_select(VarSelArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -733,54 +698,6 @@ __global__ __launch_bounds__(kSelNT) void k_var_select(VarSelArgs a) {
   if (vb == 0 && threadIdx.x == 0) VC2_STAMP(109);
 }
 
-// Round 6: the channel selection on FOUR waves (one per SIMD) with the whole array in registers for every partition round
-// (vc2_select2.h, third generation: sel3_rounds) -- D <= 256 E channels whose variances pack into 32-bit words (16-bit
-// inputs: always).  Thread t holds channels t, t + 256, ...: position p of the array = slot p / 256 of thread p % 256, which
-// is row (p / 64) of wave (p / 64) % 4 -- the layout sel3_rounds wants.  Variances that need 64-bit words take the LDS-round
-// engine on the same four waves.
-constexpr int kSel3NT = 256;
-template <int E>
-__global__ __launch_bounds__(kSel3NT) void k_chan_select3(const float* __restrict__ var_f32, int D, int k,
-                                                          uint8_t* __restrict__ mask, int* __restrict__ cols,
-                                                          int* __restrict__ perm, uint32_t* __restrict__ wperm,
-                                                          uint32_t* __restrict__ wcpos, int* status) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  using T = WordTr<uint32_t>;
-  const int tid = threadIdx.x;
-  int bad = 0;
-  if (tid == 0) VC2_STAMP(200);
-  if (tid == 0) VC2_ROUND_RAW(0, 120, 200);
-  float pre[E];
-#pragma unroll
-  for (int j = 0; j < E; ++j) { const int i = tid + j * kSel3NT; pre[j] = var_f32[i < D ? i : D - 1]; }
-#pragma unroll
-  for (int j = 0; j < E; ++j) bad |= key_fits_u32(pre[j]) ? 0 : 1;
-  if (__syncthreads_or(bad)) {
-    chan_select_body<uint64_t, kSel3NT, E>(smem, pre, D, k, mask, cols, perm, nullptr, nullptr, status);
-    if (tid == 0) VC2_STAMP(209);
-    return;
-  }
-  Sel2<uint32_t> S = sel2_carve<uint32_t>(smem, D, status);
-#if defined(VC2_DEBUG_TIMING)
-  S.dbg_slot = 0;
-#endif
-  if (tid == 0) VC2_ROUND(S, 201, D);
-  uint32_t el[E];
-#pragma unroll
-  for (int j = 0; j < E; ++j) {
-    const int i = tid + j * kSel3NT;
-    el[j] = T::pack(topk_key(pre[j]), i < D ? i : 0);
-    if (i < D) S.w[i] = el[j];
-  }
-  __syncthreads();
-  if (tid == 0) VC2_ROUND(S, 202, D);
-  constexpr int NW = kSel3NT / 64;
-  if (k >= D) { if (perm) introselect3<NW, E, 4>(S, el, D, D - 1, tid); }              // nth_element(n-1) still permutes
-  else if (k > 0 && int64_t(k) * 64 <= int64_t(D)) { if (tid == 0) s2_heap_select(S.w, 0, k, D); __syncthreads(); }   // partial_sort regime
-  else if (k > 0) introselect3<NW, E, 4>(S, el, D, k - 1, tid);
-  chan_select_epilogue<uint32_t, kSel3NT>(S, D, k, mask, cols, perm, wperm, wcpos);
-  if (tid == 0) VC2_STAMP(209);
-}
 __host__ inline size_t chan_select_lds(int D) {     // 64-bit words (the fallback), or 32-bit words + the epilogue's 128-word bitmap
   return std::max(sel2_bytes(D, 8) + 64, (sel2_bytes(D, 4) + 15) / 16 * 16 + 512 + 64);
 }
@@ -838,32 +755,21 @@ struct OrderArgs {          // the ORDER job (all null: none), done by `parts` w
   int* status;                                         // optional: the pass's status word (selection guard hits)
 };
 // workgroups for the ORDER job: 2^L arrival segments of >= 128 positions on average
-#ifndef VC2_RIDER_PARTS
-#define VC2_RIDER_PARTS 64     // rider workgroups of sweep 2 (4 waves each); 16 -> 64: the slowest rider (largest
-                               // arrival segment) sets the time: cfg2 131 -> 124 us
-#endif
-#ifndef VC2_RIDER_PARTS_LONG
-#define VC2_RIDER_PARTS_LONG 64     // ... when the sweep is expected to last > 30 us (see rider_parts_max)
-#endif
-#ifndef VC2_ORDER_PARTS
-#define VC2_ORDER_PARTS 64     // workgroups of the stand-alone k_chan_order
-#endif
-#ifndef VC2_ORDER_MINSEG
-#define VC2_ORDER_MINSEG 16
-#endif
+constexpr int kRiderParts = 64;         // rider workgroups of sweep 2 (4 waves each); 16 -> 64: the slowest rider (largest
+                                        // arrival segment) sets the time: cfg2 131 -> 124 us
+constexpr int kRiderPartsLong = 64;     // ... when the sweep is expected to last > 30 us (see rider_parts_max)
+constexpr int kOrderParts = 64;         // workgroups of the stand-alone k_chan_order
+constexpr int kOrderMinSeg = 16;
 // How many rider workgroups a sweep-2 launch carries: every rider takes one of the 512 resident workgroup slots from the
 // streaming workgroups (and the one it shares a CU with streams 40 % faster than the others: imbalance), while FEWER riders
 // take longer (16: ~26 us, 32: ~22, 64: ~20, whatever the clip) -- so a long sweep carries few, a short one many.
-// Environment VC2_RIDERS overrides (experiments).
 inline int rider_parts_max(int64_t rows, int64_t row_bytes) {
-  static const int env = [] { const char* e = getenv("VC2_RIDERS"); return e ? atoi(e) : 0; }();
-  if (env > 0) return env;
   const double sweep_us = double(rows) * double(row_bytes) / 6.5e6 + 4.0;      // ~6.5 TB/s + launch ramp
-  return sweep_us > 30.0 ? VC2_RIDER_PARTS_LONG : VC2_RIDER_PARTS;
+  return sweep_us > 30.0 ? kRiderPartsLong : kRiderParts;
 }
 __host__ inline int order_parts(int k, int max_parts) {        // a power of two
   int parts = 1;
-  while (parts * 2 <= max_parts && parts * 2 <= (k - 1) / VC2_ORDER_MINSEG) parts *= 2;
+  while (parts * 2 <= max_parts && parts * 2 <= (k - 1) / kOrderMinSeg) parts *= 2;
   return parts;
 }
 
@@ -980,14 +886,7 @@ __device__ __forceinline__ float div_via_f64(float v, double inv) { return float
 __host__ __device__ inline size_t row_lds_bytes(int D, int ES) { return (size_t(D) * ES + 15) / 16 * 16 + 16; }
 
 // Issue the DMA of one row into `rowbuf` (VEC > 1) / copy it synchronously (scalar fallback).
-// AUX = cache policy bits of the DMA (0 default, 2 = nt: streamed, not kept).
-#ifndef VC2_AUX_S2
-#define VC2_AUX_S2 0
-#endif
-#ifndef VC2_AUX_S3
-#define VC2_AUX_S3 0
-#endif
-template <int DT, int VEC, int AUX = 0>
+template <int DT, int VEC>
 __device__ __forceinline__ void row_issue(const void* __restrict__ x, int64_t row, int D, int CV,
                                           unsigned char* rowbuf, int lane) {
   constexpr int ES = Tr<DT>::ES;
@@ -1003,7 +902,7 @@ __device__ __forceinline__ void row_issue(const void* __restrict__ x, int64_t ro
       const int cv = j * 64 + lane;
       if (cv < CV)
         __builtin_amdgcn_global_load_lds((glb_void_t*)(src + int64_t(cv) * 16), (lds_void_t*)(rowbuf + j * 1024),
-                                         16, 0, AUX);
+                                         16, 0, 0);
     }
   }
 }
@@ -1371,10 +1270,6 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
   // (RIDER = 0 instantiations carry no ORDER code: it is only ever attached in "torch order" mode.)
   const int nrider = (RIDER && rider.perm) ? (rider.parts & 0xFF) : 0;
   VC2_WGTIME(1, 0);
-#ifdef VC2_RIDER_PROBE
-  if (int(blockIdx.x) >= nrider && (rider.parts >> 8) == 1) return;     // probe: riders alone
-  if (int(blockIdx.x) < nrider && (rider.parts >> 8) == 2) return;      // probe: sweep alone
-#endif
   if constexpr (RIDER != 0) {
     if (int(blockIdx.x) < nrider) {
       chan_order_body<uint32_t, kRowWaves, 4, 4>(smem, rider.var_f32, rider.D, rider.k, rider.perm, rider.cols,
@@ -1410,11 +1305,11 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
 #pragma unroll
   for (int i = 0; i < NPLB; ++i) acc[i] = 0.0;
   int n = n0 + wave;
-  if (n < n1) row_issue<DT, VEC, VC2_AUX_S2>(x, int64_t(f) * N + n, D, CV, buf0, lane);
+  if (n < n1) row_issue<DT, VEC>(x, int64_t(f) * N + n, D, CV, buf0, lane);
   for (; n < n1; n += kRowWaves) {
     const int64_t row = int64_t(f) * N + n;
     row_wait();
-    if (n + kRowWaves < n1) row_issue<DT, VEC, VC2_AUX_S2>(x, row + kRowWaves, D, CV, buf1, lane);
+    if (n + kRowWaves < n1) row_issue<DT, VEC>(x, row + kRowWaves, D, CV, buf1, lane);
     // the norm rounded to T, the "torch order" queue, the denominator (F.normalize's clamp_min), den[row]
     auto finish_norm = [&](float nrm32, int margin) -> float {
       const float norm = rnT<DT>(nrm32);
@@ -1619,16 +1514,11 @@ constexpr float kS2QuotMinBf16 = 2.3509887016445750e-38f;  // 2^-125: products b
 constexpr float kS2NormLoF16 = 6.103515625e-05f;           // 2^-14: dn a normal fp16 number
 constexpr float kS2NormHiF16 = 32768.f;
 
-#ifndef VC2_S2_PROBE
-#define VC2_S2_PROBE 0       // timing probes (results invalid): 1 memory side only (DMA + LDS reads), 2 compute only (no DMA), 3 DMA only
-#endif
-#ifndef VC2_S2_WAVES
-#define VC2_S2_WAVES 2      // waves per SIMD the register allocation aims at (3: three workgroups per CU)
-#endif
-constexpr int kS2CombineRounds = VC2_S2_WAVES >= 3 ? 4 : 2;      // (3 workgroups per CU: 4 NCH + 2 NCH KiB of LDS each)
+constexpr int kS2Waves = 2;             // waves per SIMD the register allocation aims at
+constexpr int kS2CombineRounds = 2;
 __host__ inline size_t s2v2_lds(int nch) { return size_t(kRowWaves) * nch * 1024 + size_t(kRowWaves) * (4 * nch / kS2CombineRounds) * 64 * 8; }
 template <int DT, int NCH, int RIDER, int ORD>
-__global__ __launch_bounds__(kRowWaves * 64, VC2_S2_WAVES) void k_norm_colsum2(const void* __restrict__ x, int N, const int* __restrict__ cols,
+__global__ __launch_bounds__(kRowWaves * 64, kS2Waves) void k_norm_colsum2(const void* __restrict__ x, int N, const int* __restrict__ cols,
                                                                  int strict, int S, int q, int64_t R,
                                                                  float* __restrict__ den_out, double* __restrict__ part,
                                                                  int* __restrict__ tk, unsigned long long* __restrict__ fixq,
@@ -1699,7 +1589,7 @@ __global__ __launch_bounds__(kRowWaves * 64, VC2_S2_WAVES) void k_norm_colsum2(c
   // the wave's first row is on its way before anything else is fetched
   {
     const int first = ORD ? (ord_cnt > 0 ? ord_r0 : -1) : first_row_from(row_a, f_a);
-    if (VC2_S2_PROBE != 2 && first >= 0) s2_issue_row<NCH>(row_src(first), wbuf);
+    if (first >= 0) s2_issue_row<NCH>(row_src(first), wbuf);
   }
   // LDS byte address of the lane's elements: pair k = compact positions 128 k + 2 lane, + 1
   uint32_t addr[NPLB];
@@ -1747,7 +1637,7 @@ __global__ __launch_bounds__(kRowWaves * 64, VC2_S2_WAVES) void k_norm_colsum2(c
       }
     };
     for (int i = 0; i < cnt; ++i) {
-      if (VC2_S2_PROBE != 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #ifdef VC2_DEBUG_TIMING
       if (i == 0 && seg_a == row_a) VC2_WGTIME(4, 0);
 #endif
@@ -1756,7 +1646,6 @@ __global__ __launch_bounds__(kRowWaves * 64, VC2_S2_WAVES) void k_norm_colsum2(c
       float XA[NP], XB[NP];                                       // the lane's pairs as fp32 values
 #pragma unroll
       for (int k = 0; k < NP; ++k) {
-        if (VC2_S2_PROBE == 3) { XA[k] = 1.f; XB[k] = 1.f; continue; }
         if constexpr (DT == VC2_BF16) {
           asm volatile("ds_read_u16_d16_hi %0, %2\n\tds_read_u16_d16_hi %1, %3"
                        : "=&v"(XA[k]), "=&v"(XB[k]) : "v"(addr[2 * k]), "v"(addr[2 * k + 1]) : "memory");
@@ -1769,17 +1658,8 @@ __global__ __launch_bounds__(kRowWaves * 64, VC2_S2_WAVES) void k_norm_colsum2(c
 #pragma unroll
       for (int k = 0; k < NP; ++k) asm volatile("" : "+v"(XA[k]), "+v"(XB[k]));   // (the loads' results: not before the wait)
       // the row is in registers: its buffer takes the wave's NEXT row (of this segment, else of a later one) right away
-      if (VC2_S2_PROBE != 2) {
-        const int nr = i + 1 < cnt ? r0 + RS * (i + 1) : (ORD ? -1 : first_row_from(seg_b, f + 1));
-        if (nr >= 0) s2_issue_row<NCH>(row_src(nr), wbuf);
-      }
-      if (VC2_S2_PROBE == 1 || VC2_S2_PROBE == 3) {               // (keep the loads alive, skip the arithmetic)
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < NP; ++k) t += XA[k] + XB[k];
-        if (t == 12345.678f) pk_dn = t;
-        continue;
-      }
+      const int nr = i + 1 < cnt ? r0 + RS * (i + 1) : (ORD ? -1 : first_row_from(seg_b, f + 1));
+      if (nr >= 0) s2_issue_row<NCH>(row_src(nr), wbuf);
       if constexpr (DT == VC2_F16) {
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
@@ -1893,12 +1773,8 @@ __global__ __launch_bounds__(kRowWaves * 64, VC2_S2_WAVES) void k_norm_colsum2(c
         if ((ib < 0 && (i & 15) == 15) || i == cnt - 1) {          // a block (or the leftover chain) is complete
           const int blk = ib < 0 ? ord_b0 + (i >> 4) : nblk;
           float* dst = bsum + (size_t(uint32_t(f * (nblk + 1) + blk))) * C + 2 * lane;
-#ifndef VC2_ORD_PROBE_NOSTORE
 #pragma unroll
           for (int k = 0; k < NP; ++k) *reinterpret_cast<f2_t*>(dst + 128 * k) = chain[k];
-#else
-          if (chain[0].x == 12345.678f) *dst = chain[1].x;
-#endif
         }
       }
     }
@@ -2311,10 +2187,7 @@ struct FixRiders {
   int* corr_count; NormCorr* corr; float* den;
   FixPush push;
 };
-#ifndef VC2_FIX_WAVES_DEFAULT
-#define VC2_FIX_WAVES_DEFAULT 8      // (8 = two chains per SIMD: a fp16 norm replay is ONE sequential 2048-step chain)
-#endif
-constexpr int kFixWaves = VC2_FIX_WAVES_DEFAULT;               // (default; FixRiders::waves)
+constexpr int kFixWaves = 8;      // FixRiders::waves: two chains per SIMD (a fp16 norm replay is ONE sequential 2048-step chain)
 constexpr int kTkFixEntries = 8;             // ticket word: correction entries of the pass (FixPush)
 constexpr int kTkSelArrive = 9;              // ticket word: k_select workgroups that have finished their selection (host mirror)
 
@@ -3086,17 +2959,8 @@ __host__ __device__ inline int dist_split_cut(int j, int S, int N, int skew_q10)
   return int((num + den / 2) / den);
 }
 
-// V2 = 1 ("streamlined", round 5; 16-bit rows of full 1 KiB chunks, C = 64 NPLB = D / 2, ACC = 1, QUAD tables): the row
-// loop of k_norm_colsum2 -- the row's elements are read into registers first (bf16 with ds_read_u16_d16_hi: the element
-// arrives as its fp32 value), the wave's NEXT row is DMA'd into the same buffer at once and lands while this one is
-// computed; LDS addresses are per-lane constants; the rows' denominators / exact-division flags are parked in lanes (no LDS
-// access in the loop: the compiler would put a vmcnt(0) in front of it); the first row's DMA is issued before the tables
-// are fetched.  fp16 divides by the fused-multiply-add quotient proved in tests/tools/check_f16_quotient.c.
-#ifndef VC2_S3_WAVES
-#define VC2_S3_WAVES 3      // (at 4 the streamlined loop spills inside the row loop)
-#endif
-template <int DT, int VEC, int NPLB, int ACC, int QUAD = 0, int V2 = 0>
-__global__ __launch_bounds__(kRowWaves * 64, V2 ? VC2_S3_WAVES : 1) void k_dist(const void* __restrict__ x, int N, int D, int CV, int C,
+template <int DT, int VEC, int NPLB, int ACC, int QUAD = 0>
+__global__ __launch_bounds__(kRowWaves * 64, 1) void k_dist(const void* __restrict__ x, int N, int D, int CV, int C,
                                                          const int* __restrict__ cols,
                                                          const int* __restrict__ spos, int strict, int S,
                                                          int rows_per_split, int skew_q10, const float* __restrict__ den,
@@ -3134,30 +2998,16 @@ __global__ __launch_bounds__(kRowWaves * 64, V2 ? VC2_S3_WAVES : 1) void k_dist(
   int n = n0 + wave;
   if (tid == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1)) VC2_STAMP(700);
   VC2_WGTIME(2, 0);
-  static_assert(V2 == 0 || (QUAD != 0 && ACC == 1 && VEC > 1 && DT != VC2_F32 && NPLB % 4 == 0), "streamlined sweep 3");
-  constexpr int NCH2 = NPLB / 4;                                    // (V2) 1 KiB chunks per row
-  const unsigned char* xl2 = static_cast<const unsigned char*>(x) + (size_t(f) * N + n) * (size_t(D) * ES) + size_t(lane) * 16;   // (V2) the wave's first row, this lane's 16 bytes
-  const int cnt2 = wave < nrows ? (nrows - wave + kRowWaves - 1) / kRowWaves : 0;                    // (V2) the wave's rows
-  float my_dn = 1.f;                                                // (V2) lane j: the wave's row j
-  uint32_t my_rf = 1u;
-  if constexpr (V2 != 0) {
-    if (cnt2 > 0) s2_issue_row<NCH2>(xl2, buf0);
-    if (lane < cnt2) {
-      const int64_t row = int64_t(f) * N + n + kRowWaves * lane;
-      my_dn = den[row];
-      my_rf = rflag ? uint32_t(rflag[row]) : 1u;
-    }
-  }
-  if constexpr (V2 == 0) {
+  // (unused, kept on purpose: the extra use of this offset steers the optimiser to the instruction sequence every k_dist
+  //  instantiation has been measured with -- without it the register allocation moves, e.g. 109 -> 107 VGPRs)
+  const size_t row0_bytes = (size_t(f) * N + n) * (size_t(D) * ES);
+  (void)row0_bytes;
   if (lane < 4) reinterpret_cast<uint32_t*>(buf0 + rowb - 16)[lane] = 0u;
   if (tid < 2) lcount[tid] = 0;
   for (int r = tid; r < nrows; r += kRowWaves * 64) {
     dens[r] = den[int64_t(f) * N + n0 + r];
     rfl[r] = ((kFast || (ACC == 1 && DT == VC2_F16)) && rflag) ? rflag[int64_t(f) * N + n0 + r] : 1;   // (fp16: written by k_norm_colsum2 only -- else null)
   }
-  }
-  float den_mine = 0.f;                                             // (V2) dens[tid], stored to LDS behind the table loads
-  if constexpr (V2 != 0) { if (tid < nrows) den_mine = den[int64_t(f) * N + n0 + tid]; }
   int coff[NPLB];
   float cv[NPLB], cf[NPLB];                                       // video / frame centre of the lane's compact positions
   // QUAD (ACC = 1 only: any ownership of the compact positions gives the same bits there -- the accumulation is bounded,
@@ -3230,12 +3080,7 @@ __global__ __launch_bounds__(kRowWaves * 64, V2 ? VC2_S3_WAVES : 1) void k_dist(
   }
   // (plain loads first: behind an in-flight global_load_lds the compiler waits for EVERY load separately)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  if constexpr (V2 != 0) {
-    if (tid < 2) lcount[tid] = 0;
-    if (tid < nrows) dens[tid] = den_mine;                          // (phase 2 reads them; nrows <= kDistMaxRows <= 256)
-  } else {
-  if (n < n1) row_issue<DT, VEC, VC2_AUX_S3>(x, int64_t(f) * N + n, D, CV, buf0, lane);
-  }
+  if (n < n1) row_issue<DT, VEC>(x, int64_t(f) * N + n, D, CV, buf0, lane);
   __syncthreads();
   // ---- phase 1 ---------------------------------------------------------------------------------------
   // The rows' results stay in registers (lane `it` holds row it of this wave) until the loop is over: the compiler
@@ -3254,113 +3099,9 @@ __global__ __launch_bounds__(kRowWaves * 64, V2 ? VC2_S3_WAVES : 1) void k_dist(
   };
   float held_v = 0.f, held_f = 0.f;                               // (fast path) the previous row's lane partials
   int it = 0;
-  if constexpr (V2 != 0) {
-    constexpr int NP = NPLB / 2;
-    typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-    uint32_t addr[NPLB];                                            // LDS byte address of the lane's elements
-    {
-      const uint32_t base = uint32_t(uintptr_t((lds_void_t*)buf0));
-#pragma unroll
-      for (int i = 0; i < NPLB; ++i) addr[i] = base + uint32_t(coff[i]) * uint32_t(ES);
-    }
-    // fp16: the centres as packed pairs
-    uint32_t cvp[DT == VC2_F16 ? NP : 1], cfp[DT == VC2_F16 ? NP : 1];
-    if constexpr (DT == VC2_F16) {
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        union { h2_t h; uint32_t u; } a, b;
-        a.h = __builtin_convertvector((f2_t){cv[2 * k], cv[2 * k + 1]}, h2_t);
-        b.h = __builtin_convertvector((f2_t){cf[2 * k], cf[2 * k + 1]}, h2_t);
-        cvp[k] = a.u; cfp[k] = b.u;
-      }
-    }
-    const size_t row_step = size_t(kRowWaves) * size_t(D) * ES;
-    for (; it < cnt2; ++it) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      float XA[NP], XB[NP];
-#pragma unroll
-      for (int k = 0; k < NP; ++k) {
-        if constexpr (DT == VC2_BF16)
-          asm volatile("ds_read_u16_d16_hi %0, %2\n\tds_read_u16_d16_hi %1, %3"
-                       : "=&v"(XA[k]), "=&v"(XB[k]) : "v"(addr[2 * k]), "v"(addr[2 * k + 1]) : "memory");
-        else
-          asm volatile("ds_read_u16 %0, %2\n\tds_read_u16 %1, %3"
-                       : "=&v"(XA[k]), "=&v"(XB[k]) : "v"(addr[2 * k]), "v"(addr[2 * k + 1]) : "memory");
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-      for (int k = 0; k < NP; ++k) asm volatile("" : "+v"(XA[k]), "+v"(XB[k]));
-      if (it + 1 < cnt2) s2_issue_row<NCH2>(xl2 + size_t(it + 1) * row_step, buf0);
-      const float dn = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_dn), it));
-      const bool exact_div = __builtin_amdgcn_readlane(int(my_rf), it) != 0;
-      float pv = 0.f, pf = 0.f;
-      if constexpr (DT == VC2_BF16) {
-        using AR = DistArith<VC2_BF16, 1>;
-        auto body = [&](auto exact_tag) {
-          constexpr bool kExact = decltype(exact_tag)::value;
-          const double inv = kExact ? 1.0 / double(dn) : 0.0;
-          const float r = kExact ? 0.f : __builtin_amdgcn_rcpf(dn);
-#pragma unroll
-          for (int k = 0; k < NP; ++k) {
-            uint32_t xh;
-            if constexpr (kExact) xh = AR::pk(div_via_f64(XA[k], inv), div_via_f64(XB[k], inv));
-            else { const f2_t pr = pk_mul_f32((f2_t){XA[k], XB[k]}, (f2_t){r, r}); xh = AR::pk(pr.x, pr.y); }
-            const float xa = __uint_as_float(xh << 16), xb = __uint_as_float(xh & 0xFFFF0000u);
-            const uint32_t dv = AR::pk(xa - cv[2 * k], xb - cv[2 * k + 1]);
-            const uint32_t df = AR::pk(xa - cf[2 * k], xb - cf[2 * k + 1]);
-            const float va = __uint_as_float(dv << 16), vb = __uint_as_float(dv & 0xFFFF0000u);
-            const float fa = __uint_as_float(df << 16), fb = __uint_as_float(df & 0xFFFF0000u);
-            pv = AR::dot_ones(AR::pk(va * va, vb * vb), pv);
-            pf = AR::dot_ones(AR::pk(fa * fa, fb * fb), pf);
-          }
-        };
-        if (exact_div) body(std::true_type{}); else body(std::false_type{});
-      } else {
-        const h2_t ones = {static_cast<_Float16>(1.0f), static_cast<_Float16>(1.0f)};
-        auto body = [&](auto exact_tag) {
-          constexpr bool kExact = decltype(exact_tag)::value;
-          const double inv = kExact ? 1.0 / double(dn) : 0.0;
-          const float r = kExact ? 0.f : __builtin_amdgcn_rcpf(dn);
-          const f2_t r2 = {r, r}, d2 = {dn, dn};
-#pragma unroll
-          for (int k = 0; k < NP; ++k) {
-            union { uint16_t u; _Float16 h; } ca, cb;
-            ca.u = uint16_t(__float_as_uint(XA[k])); cb.u = uint16_t(__float_as_uint(XB[k]));
-            const f2_t xx = {float(ca.h), float(cb.h)};
-            h2_t xh;
-            if constexpr (kExact) xh = __builtin_convertvector((f2_t){div_via_f64(xx.x, inv), div_via_f64(xx.y, inv)}, h2_t);
-            else {
-              const f2_t q0 = pk_mul_f32(xx, r2);
-              const f2_t e = pk_fnma_f32(d2, q0, xx);
-              xh = __builtin_convertvector(pk_fma_f32(e, r2, q0), h2_t);
-            }
-            union { uint32_t u; h2_t h; } a, b;
-            a.u = cvp[k]; b.u = cfp[k];
-            const h2_t dv = xh - a.h, df = xh - b.h;
-            pv = __builtin_amdgcn_fdot2(dv * dv, ones, pv, false);
-            pf = __builtin_amdgcn_fdot2(df * df, ones, pf, false);
-          }
-        };
-        if (exact_div) body(std::true_type{}); else body(std::false_type{});
-      }
-      // two rows' lane partials are reduced together (four values: one permlane32 / permlane16 fold each)
-      if (it & 1) {
-        float q[4] = {held_v, held_f, pv, pf};
-        wave_totals_f32<4>(q);
-        auto at = [&](int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(q[0]), l)); };
-        const float t0 = at(0), t2 = at(16), t1 = at(32), t3 = at(48);
-        settle(t0, t1, it - 1);
-        settle(t2, t3, it);
-      } else {
-        held_v = pv; held_f = pf;
-      }
-    }
-    if (it & 1) settle(wave_sum_bcast_f32(held_v), wave_sum_bcast_f32(held_f), it - 1);   // the odd row out
-  } else
   for (; n < n1; n += kRowWaves, ++it) {
     // issue the row's DMA, wait, compute straight from LDS
-    if (it) row_issue<DT, VEC, VC2_AUX_S3>(x, int64_t(f) * N + n, D, CV, buf0, lane);
+    if (it) row_issue<DT, VEC>(x, int64_t(f) * N + n, D, CV, buf0, lane);
     row_wait();
     const float dn = dens[n - n0];
     const bool exact_div = !(kFast || (ACC == 1 && DT == VC2_F16)) || rfl[n - n0] != 0;
@@ -3452,7 +3193,7 @@ __global__ __launch_bounds__(kRowWaves * 64, V2 ? VC2_S3_WAVES : 1) void k_dist(
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");       // LDS reads done before the buffer is refilled
   }
-  if constexpr (kFast && V2 == 0) {
+  if constexpr (kFast) {
     if (it & 1) settle(wave_sum_bcast_f32(held_v), wave_sum_bcast_f32(held_f), it - 1);   // the odd row out
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -3482,7 +3223,7 @@ __global__ __launch_bounds__(kRowWaves * 64, V2 ? VC2_S3_WAVES : 1) void k_dist(
       const double inv = 1.0 / double(dens[nl]);
       const float* cen = which ? fc + int64_t(f) * C : vc;
       if (dma) {
-        if (wave == 0) row_issue<DT, VEC, VC2_AUX_S3>(x, row, D, CV, smem, lane);
+        if (wave == 0) row_issue<DT, VEC>(x, row, D, CV, smem, lane);
         int colv[kP2], sppv[kP2];
         float cev[kP2];
 #pragma unroll
@@ -3748,21 +3489,12 @@ __device__ __forceinline__ void select_frame_body(unsigned char* smem, const flo
   if (N > sel2_capacity(1, 4)) topk_smallest2<W, 4, 4, 8>(S, N, k, tid);
   else if (tid < 64) {
     // round 6: 32-bit words, frames of <= 512 tokens: barrier-free rounds on registers (sel4_round<1, true>; the LDS rounds
-    // cost 1.2-1.8 us each above 64 elements, these 0.7-0.8).  -DVC2_NO_SEL4_SOLO: the LDS rounds of rounds 3-5;
-    // -DVC2_SEL3_SOLO: the ballot form (sel3_rounds; measured no faster than the LDS rounds)
-#if !defined(VC2_NO_SEL4_SOLO) && !defined(VC2_SEL3_SOLO)
+    // cost 1.2-1.8 us each above 64 elements, these 0.7-0.8)
     if constexpr (sizeof(W) == 4) {
       if (N <= 256) topk_smallest4_solo<4>(S, N, k, tid);
       else if (N <= 512) topk_smallest4_solo<8>(S, N, k, tid);
       else topk_smallest2<W, 1, 4, 4>(S, N, k, tid);
     } else
-#elif defined(VC2_SEL3_SOLO)
-    if constexpr (sizeof(W) == 4) {
-      if (N <= 256) topk_smallest3_solo<4>(S, N, k, tid);
-      else if (N <= 512) topk_smallest3_solo<8>(S, N, k, tid);
-      else topk_smallest2<W, 1, 4, 4>(S, N, k, tid);
-    } else
-#endif
     topk_smallest2<W, 1, 4, 4>(S, N, k, tid);
   }
   __syncthreads();
@@ -4037,15 +3769,12 @@ __device__ __forceinline__ void copy_row(const unsigned char* __restrict__ s, un
   if ((row_bytes & 15) == 0 && ((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15) == 0) {
     const int64_t nv = row_bytes >> 4;
     for (int64_t t = threadIdx.x; t < nv; t += blockDim.x) {
-#ifndef VC2_GATHER_NO_NT      // streaming stores: the kept rows are consumed much later (gather 16.1 -> 15.5 us)
+      // streaming stores: the kept rows are consumed much later (gather 16.1 -> 15.5 us)
       const uint4 v = reinterpret_cast<const uint4*>(s)[t];                     // (non-temporal loads too: no difference)
       __builtin_nontemporal_store(v.x, &reinterpret_cast<uint32_t*>(d)[4 * t]);
       __builtin_nontemporal_store(v.y, &reinterpret_cast<uint32_t*>(d)[4 * t + 1]);
       __builtin_nontemporal_store(v.z, &reinterpret_cast<uint32_t*>(d)[4 * t + 2]);
       __builtin_nontemporal_store(v.w, &reinterpret_cast<uint32_t*>(d)[4 * t + 3]);
-#else
-      reinterpret_cast<uint4*>(d)[t] = reinterpret_cast<const uint4*>(s)[t];
-#endif
     }
   } else {
     for (int64_t t = threadIdx.x; t < row_bytes; t += blockDim.x) d[t] = s[t];
@@ -4275,6 +4004,17 @@ std::atomic<int> g_mode_default{4};
 thread_local int g_mode_thread = -1;             // -1: follow the process-wide setting
 inline int cur_mode() { return g_mode_thread >= 0 ? g_mode_thread : g_mode_default.load(std::memory_order_relaxed); }
 
+// Test seams, the library's only environment reads.  Each switch, set to 0, forces a route that the library also takes on
+// its own for other inputs, so that tests/test_gpu_parity.py can run that route on any fixture.  Read per pass (the suite
+// flips them inside one process), each where it is decided:
+//   VC2_S2_ORD=0  sweep 2 without the ORD form (k_norm_colsum2<.., 0>, margins and replays): plans with ord_m == 0;
+//   VC2_SEL4=0    the LDS-round k_chan_select: D > 4096 or 64-bit words;
+//   VC2_VARSEL=0  the variance and the selection in two launches: fp32, D > 4096, HAVE_STATS, profiling, < 16 CUs.
+inline bool test_seam_on(const char* name) {
+  const char* e = getenv(name);
+  return !e || atoi(e) != 0;
+}
+
 int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total = 0, int block_frames = 0) {
   if (F <= 0 || N <= 0 || D <= 0) return fail(VC2_ERR_ARG, "F, N, D must be positive (got %lld, %lld, %lld)",
                                               (long long)F, (long long)N, (long long)D);
@@ -4291,8 +4031,8 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
   p->F_total = F_total > 0 ? F_total : F;
   // sweep-1 groups: `stat_splits` pieces per frame -- a function of the WHOLE video's frame count, so that every
   // rank of a frame-sharded pass cuts its frames exactly like the unsharded pass does
-  static const int env_groups = [] { const char* e = getenv("VC2_STAT_GROUPS"); return e ? atoi(e) : 128; }();   // (experiments: row groups aimed at)
-  p->stat_splits = int(std::max<int64_t>(1, std::min<int64_t>(cdiv(env_groups, p->F_total), std::max<int64_t>(1, N / 32))));
+  constexpr int64_t kStatGroups = 128;                             // row groups aimed at
+  p->stat_splits = int(std::max<int64_t>(1, std::min<int64_t>(cdiv(kStatGroups, p->F_total), std::max<int64_t>(1, N / 32))));
   p->rows_per_group = int(cdiv(N, p->stat_splits));
   p->stat_splits = int(cdiv(N, p->rows_per_group));
   p->G = int(F * p->stat_splits);
@@ -4311,11 +4051,7 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
     // frame-aligned cut was 4 x 49 rows for half of the frames and 3 x 66 for the others -- the sweep took as long as
     // the 66-row workgroups (36 us against 25 for the others: scripts/dbg_wg.py).  A chunk that contains a frame
     // boundary is swept segment by segment (one flush of the column sums per segment).
-    // (the streamlined sweep built for three workgroups per CU -- VC2_S2_WAVES = 3 -- has 768 slots: 512 streaming
-    // workgroups AND the riders are resident together; decided from what the plan knows, shape and mode)
-    static const int env_budget = [] { const char* e = getenv("VC2_S2_BUDGET"); return e ? atoi(e) : 0; }();
-    const bool three = VC2_S2_WAVES >= 3 && cur_mode() != 0 && dt != VC2_F32 && (D == 1024 || D == 3584 || D == 4096);
-    const int64_t budget = env_budget > 0 ? env_budget : (three ? 512 : 512 - riders);
+    const int64_t budget = 512 - riders;
     int64_t W = std::max<int64_t>(1, std::min<int64_t>(budget, p->R / (8 * kRowWaves)));   // >= 32 rows a chunk
     int64_t q = std::max<int64_t>(cdiv(p->R, W), cdiv(N, 6));          // (a frame meets at most (N - 1) / q + 2 <= 8 chunks)
     p->S_q = int(q);
@@ -4340,24 +4076,14 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
   {
     // sweep 3: one workgroup per (frame, split); ~1024 workgroups when the video allows, and at most 25 rows each so
     // that the 10 exp per token of the fused epilogue are ONE round over the workgroup's 256 threads
-#ifndef VC2_DIST_WGS
-#define VC2_DIST_WGS 1024
-#endif
-#ifndef VC2_DIST_RPS_MIN
-#define VC2_DIST_RPS_MIN 16
-#endif
-    int64_t rps = std::max<int64_t>(VC2_DIST_RPS_MIN, std::min<int64_t>(25, cdiv(p->R, VC2_DIST_WGS)));
-    static const int env_rps = [] { const char* e = getenv("VC2_DIST_RPS"); return e ? atoi(e) : 0; }();   // (experiments)
-    if (env_rps > 0) rps = std::min<int64_t>(env_rps, kDistMaxRows);
+    constexpr int64_t kDistWgs = 1024, kDistRpsMin = 16;
+    int64_t rps = std::max<int64_t>(kDistRpsMin, std::min<int64_t>(25, cdiv(p->R, kDistWgs)));
     rps = std::min<int64_t>(rps, N);
     p->S2 = int(cdiv(N, rps));
-#ifndef VC2_DIST_SKEW
-#define VC2_DIST_SKEW 138
-#endif
     // the skew pays when the launch is ONE wave of workgroups with several of them per CU (4 at 1024 on 256 CUs)
+    constexpr int64_t kDistSkew = 138;
     const int64_t wgs = F * p->S2;
-    static const int env_skew = [] { const char* e = getenv("VC2_DIST_SKEW_Q10"); return e ? atoi(e) : -1; }();
-    p->skew2_q10 = env_skew >= 0 ? env_skew : (p->S2 >= 4 && wgs > 512 && wgs <= 1024) ? int(VC2_DIST_SKEW * (wgs - 256) / 768) : 0;
+    p->skew2_q10 = (p->S2 >= 4 && wgs > 512 && wgs <= 1024) ? int(kDistSkew * (wgs - 256) / 768) : 0;
     p->rows_per_split2 = dist_split_cut(1, p->S2, int(N), p->skew2_q10);          // the longest split
   }
   size_t o = 0;
@@ -4490,20 +4216,14 @@ int launch_chan_stats(const Plan& p, const void* x, void* ws, double* bstats, vo
   if (var_f32 || var_T) {
     const int64_t n_each = int64_t(p.BF) * p.N, n_last = p.R - int64_t(p.NB - 1) * n_each;
     // narrow column slabs (16 columns x 16 lanes: 224 workgroups at D = 3584) spread the loads of sweep 1's partials
-    // (7 MB) over the whole chip instead of 56 CUs; VC2_VAR_CW = 64 is the wide form (experiments)
-    static const int cw_env = [] { const char* e = getenv("VC2_VAR_CW"); return e ? atoi(e) : 16; }();
-    auto go = [&](auto dt_tag, auto cw_tag) {
-      constexpr int DT = decltype(dt_tag)::value, CW = decltype(cw_tag)::value;
-      hipLaunchKernelGGL((k_var_from_stats<DT, CW>), dim3(unsigned(cdiv(p.D, CW))), dim3(CW * kRedGL), 0, st,
+    // (7 MB) over the whole chip instead of 56 CUs
+    constexpr int CW = 16;
+    VC2_DISPATCH_DT(p.dt, hipLaunchKernelGGL((k_var_from_stats<DT, CW>), dim3(unsigned(cdiv(p.D, CW))), dim3(CW * kRedGL), 0, st,
                          (const double*)nullptr, p.NB, n_each, n_last, int(p.D), var_T, var_f32,
                          zero_queue_counters ? wsp<int>(ws, p.o_ticket) : (int*)nullptr, src,
                          make_fold_tab(p.NB, n_each, n_last),
                          zero_queue_counters ? wsp<unsigned long long>(ws, p.o_nfixlist) : nullptr,
-                         int(p.R + cdiv(p.F, 2)), reinterpret_cast<unsigned long long*>(kstatus));
-    };
-    VC2_DISPATCH_DT(p.dt, (cw_env == 64 ? go(std::integral_constant<int, DT>{}, std::integral_constant<int, 64>{})
-                           : cw_env == 32 ? go(std::integral_constant<int, DT>{}, std::integral_constant<int, 32>{})
-                                          : go(std::integral_constant<int, DT>{}, std::integral_constant<int, 16>{})));
+                         int(p.R + cdiv(p.F, 2)), reinterpret_cast<unsigned long long*>(kstatus)));
   } }
   return check_launch("chan_stats");
 }
@@ -4533,25 +4253,12 @@ int launch_chan_select(const float* var_f32, int64_t D, int64_t k, uint8_t* mask
   if (k <= 0 || k > D) return fail(VC2_ERR_UNSUPPORTED, "channel count k=%lld out of range for D=%lld",
                                    (long long)k, (long long)D);
   const size_t smem = chan_select_lds(int(D));
-  // VC2_SEL3=1 (experiment, round 6; OFF by default): D <= 4096 on four waves with the array in registers (k_chan_select3).
-  // Bit-identical (409 selection / full-pass tests green with it) and SLOWER: 26.1 against 20.9 us at D = 3584 -- its
-  // rounds are ~70 instructions per 64-element row with VALU -> SGPR -> VALU dependencies that one wave per SIMD cannot hide
-  // (4.2 / 3.0 / 2.3 / 2.4 us for the rounds the 16-wave LDS form does in 2.0 each: profiles/r06_b_sel3_register_rounds.csv)
-  const int sel3_env = [] { const char* e = getenv("VC2_SEL3"); return e ? atoi(e) : 0; }();     // (read per call: the test-suite
-  //                                                                                                   compares the forms in one process)
-  // VC2_SEL4 (default 1): D <= 4096, sixteen waves, thread-contiguous registers (k_chan_select4); 0: the LDS rounds
-  const int sel4_env = [] { const char* e = getenv("VC2_SEL4"); return e ? atoi(e) : 1; }();
-  if (sel4_env != 0 && sel3_env == 0 && D <= 4096 && !words64_expected) {
+  // D <= 4096: sixteen waves, thread-contiguous registers (k_chan_select4); else (and VC2_SEL4=0) the LDS rounds
+  if (test_seam_on("VC2_SEL4") && D <= 4096 && !words64_expected) {
     { int rca = allow_big_lds(&k_chan_select4, smem, "k_chan_select4"); if (rca) return rca; }
     ProfScope ps_(KID_CHAN_SELECT, st);
     hipLaunchKernelGGL(k_chan_select4, dim3(1), dim3(kSelNT), smem, st, var_f32, int(D), int(k), mask, cols, perm, wperm, wcpos, status);
     return check_launch("chan_select4");
-  }
-  if (sel3_env != 0 && D <= 4096 && !words64_expected) {
-    ProfScope ps_(KID_CHAN_SELECT, st);
-    { int rca = allow_big_lds(&k_chan_select3<16>, smem, "k_chan_select3"); if (rca) return rca; }
-    hipLaunchKernelGGL(k_chan_select3<16>, dim3(1), dim3(kSel3NT), smem, st, var_f32, int(D), int(k), mask, cols, perm, wperm, wcpos, status);
-    return check_launch("chan_select3");
   }
   { int rca = allow_big_lds(&k_chan_select, smem, "k_chan_select"); if (rca) return rca; }
   { ProfScope ps_(KID_CHAN_SELECT, st);
@@ -4564,7 +4271,7 @@ int launch_chan_order(const OrderArgs& oa, hipStream_t st) {
   const size_t smem = chan_order_lds(oa.D, oa.k, 8);
   { int rca = allow_big_lds(&k_chan_order, smem, "k_chan_order"); if (rca) return rca; }
   { ProfScope ps_(KID_CHAN_ORDER, st);
-  hipLaunchKernelGGL(k_chan_order, dim3(unsigned(order_parts(oa.k, VC2_ORDER_PARTS))), dim3(kOrdNT), smem, st, oa); }
+  hipLaunchKernelGGL(k_chan_order, dim3(unsigned(order_parts(oa.k, kOrderParts))), dim3(kOrdNT), smem, st, oa); }
   return check_launch("chan_order");
 }
 
@@ -4590,11 +4297,7 @@ inline bool fast_acc(const Plan& p, const ChanSet& cs) { return cs.strict != 0 &
 template <int DT, int VEC, int NPLB, int ACC>
 int launch_norm_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, const OrderArgs& rider, hipStream_t st) {
   const int* cols = cs.cols; const int C = cs.C;
-#ifdef VC2_NO_RIDER
-  constexpr int RIDER = 0;
-#else
   constexpr int RIDER = (ACC == 1 && VEC > 1) ? 1 : 0;       // the kernels that can carry the ORDER rider
-#endif
   if (rider.perm && !RIDER) return fail(VC2_ERR_UNSUPPORTED, "internal: ORDER rider on a sweep without one");
   size_t smem = std::max<size_t>(2 * kRowWaves * row_lds_bytes(int(p.D), Tr<DT>::ES),
                                  size_t(kRowWaves) * NPLB * 64 * 8);               // row buffers, then the combine
@@ -4609,40 +4312,17 @@ int launch_norm_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, c
   return VC2_OK;
 }
 // the streamlined sweep 2 (k_norm_colsum2): 16-bit rows of NCH full 1 KiB chunks, C = D / 2, "torch order" mode
-#ifndef VC2_S2_V2
-#define VC2_S2_V2 1
-#endif
-std::atomic<int> g_s2v2{-1};            // -1: not read yet (environment VC2_S2_V2, default: on)
-inline bool s2v2_on() {
-  int v = g_s2v2.load(std::memory_order_relaxed);
-  if (v < 0) { const char* e = getenv("VC2_S2_V2"); v = e ? (atoi(e) != 0) : VC2_S2_V2; g_s2v2.store(v, std::memory_order_relaxed); }
-  return v != 0;
-}
-std::atomic<int> g_s3v2{-1};            // the streamlined sweep 3 (k_dist<.., V2 = 1>): environment VC2_S3_V2; default OFF -- measured
-                                        // no faster than the general form (35.4 vs 34.6 us bf16, 47 vs 45 fp16: NOTES_r05.md)
-inline bool s3v2_on() {
-  int v = g_s3v2.load(std::memory_order_relaxed);
-  if (v < 0) { const char* e = getenv("VC2_S3_V2"); v = e ? (atoi(e) != 0) : 0; g_s3v2.store(v, std::memory_order_relaxed); }
-  return v != 0;
-}
 inline int s2v2_nch(const Plan& p, const ChanSet& cs) {
-  if (!s2v2_on() || p.dt == VC2_F32 || p.VEC == 1 || !cs.cols || !fast_acc(p, cs)) return 0;
+  if (p.dt == VC2_F32 || p.VEC == 1 || !cs.cols || !fast_acc(p, cs)) return 0;
   if (p.D % 512 != 0 || int64_t(cs.C) * 2 != p.D || p.R >= (int64_t(1) << 31) || p.F * int64_t(p.S) >= (int64_t(1) << 31) / 8) return 0;
   const int nch = int(p.D / 512);
   return (nch == 2 || nch == 7 || nch == 8) ? nch : 0;
 }
 // the ORD form of sweep 2 + centre kernels (torch-ordered frame sums): when the plan has a geometry for it and the
-// streamlined sweep applies.  OPT-IN (environment VC2_S2_ORD=1): bit-identical results (the whole parity suite passes
-// with it, no frame mean is ever replayed), but a wave must sweep whole 16-row blocks, which leaves 384 workgroups of
-// 64 / 68 rows where the row-interleaved form has 448 of 56 -- the busiest CU streams 132 rows instead of 112: sweep 2
-// 30.6 -> 34.7 us at the target shape, more than the centre kernels win there (fp16: -14 us in k_video_centre, +9 in the
-// sweep).  NOTES_r05.md.
-#ifndef VC2_S2_ORD_DEFAULT
-#define VC2_S2_ORD_DEFAULT 1
-#endif
+// streamlined sweep applies.  The default since round 6 (VC2_S2_ORD=0: the row-interleaved form, see test_seam_on): no frame
+// mean is ever listed or replayed, for a slightly slower sweep 2 (k_norm_colsum2; NOTES_r05.md).
 inline bool ord_on(const Plan& p, const ChanSet& cs) {
-  const char* e = getenv("VC2_S2_ORD");                          // (read per pass: the test-suite runs both forms in one process)
-  return (e ? atoi(e) : VC2_S2_ORD_DEFAULT) != 0 && p.ord_m > 0 && s2v2_nch(p, cs) != 0;
+  return test_seam_on("VC2_S2_ORD") && p.ord_m > 0 && s2v2_nch(p, cs) != 0;
 }
 template <int DT, int NCH>
 int launch_norm_v2(const Plan& p, const void* x, const ChanSet& cs, void* ws, const OrderArgs& rider, hipStream_t st) {
@@ -4715,9 +4395,6 @@ int launch_dist_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, c
                        wsp<float>(ws, p.o_fc), o.v_T, o.f_T, o.total, wsp<double>(ws, p.o_vpart));
     return VC2_OK;
   };
-  if constexpr (ACC == 1 && NPLB % 4 == 0 && DT != VC2_F32 && VEC > 1 && (NPLB == 8 || NPLB == 28 || NPLB == 32)) {
-    if (s3v2_on() && s2v2_nch(p, cs) * 4 == NPLB) return launch(k_dist<DT, VEC, NPLB, ACC, 1, 1>);   // streamlined (sweep 2 wrote rflag)
-  }
   if constexpr (ACC == 1 && NPLB % 4 == 0) {
     if (cols && (C & 3) == 0) return launch(k_dist<DT, VEC, NPLB, ACC, 1>);      // tables in 16-byte loads
   }
@@ -4740,9 +4417,7 @@ int launch_dist_t(const Plan& p, const void* x, const ChanSet& cs, void* ws, con
 // sweep 2 + centres.  single_rank: also the video centre; else only the rank's csum (for the all-gather).
 // The two strict-mode queue counters (ticket[2], ticket[3]) must be zero on entry (zero_counters).
 // rider: an ORDER job (chan_order_body) attached to sweep 2 -- it produces cs.spos for the fix-up kernels.
-#ifndef VC2_FRAME_A
-#define VC2_FRAME_A 4
-#endif
+constexpr double kFrameA = 4.0;      // kk_a of mode 4's frame-mean margin, (kk_a A / n + 4 |q|) u: see k_frame_centres
 int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, bool single_rank, hipStream_t st,
                   const OrderArgs& rider = OrderArgs{}, bool own_stats = false) {
   // (ws holds sweep 1's partials of x -- every caller ran the statistics sweep with this workspace: they bound
@@ -4761,9 +4436,6 @@ int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, boo
     ride = OrderArgs{};
   }
   if (ride.perm) ride.parts = order_parts(ride.k, rider_parts_max(p.R, p.D * p.ES));
-#ifdef VC2_RIDER_PROBE
-  if (ride.perm) { const char* e = getenv("VC2_RIDER_PROBE_MODE"); if (e) ride.parts |= atoi(e) << 8; }
-#endif
   { ProfScope ps_(KID_NORM_COLSUM, st);
   int rc = VC2_OK;
   VC2_DISPATCH_VEC(p, rc = VC2_DISPATCH_NPL(npl, launch_norm_t, p, x, cs, ws, ride, st));
@@ -4775,12 +4447,8 @@ int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, boo
   const bool replays = cs.strict != 0 && p.dt != VC2_F32;
   const int rcap = int(std::min<int64_t>(p.F * int64_t(C), INT32_MAX / 2));      // regular entries: every mean at most once
   const int rcap2 = int(p.F * cdiv(C, 64));                                        // correction entries: every (frame, column block) once
-#ifdef VC2_NO_FUSED_FIX
-  const bool fused = false;
-#else
   const bool fused = replays && single_rank && !g_prof && p.VEC > 1 && npl <= 32 && (((p.N >> 4) + 15) >> 4) <= kCFixSolo &&
                      p.F * int64_t(C) <= INT32_MAX / 2;
-#endif
   if (cs.strict && !fused) {
     ProfScope ps_(KID_OTHER, st);
     int rc = VC2_OK;
@@ -4793,10 +4461,8 @@ int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, boo
   const int bxn = int(cdiv(C, 64));
   // (a rider workgroup is as large as a frame workgroup -- 16 waves -- and with ~120 VGPRs only ONE workgroup fits a CU:
   // every rider workgroup takes a whole CU for the length of its rows' chains.  So few of them with many busy waves.)
-  static const int env_fw = [] { const char* e = getenv("VC2_FIX_WAVES"); return e ? atoi(e) : 0; }();
   const size_t fix_row = (std::max(row_lds_bytes(int(p.D), p.ES), size_t(C) * 4 + 16) + 15) / 16 * 16;
-  int fwaves = env_fw > 0 ? env_fw : VC2_FIX_WAVES_DEFAULT;
-  fwaves = int(std::max<int64_t>(1, std::min<int64_t>(std::min(fwaves, kCentreFL), int64_t(160 * 1024 - 256 - 24 * 1024) / int64_t(fix_row))));
+  const int fwaves = int(std::max<int64_t>(1, std::min<int64_t>(std::min(kFixWaves, kCentreFL), int64_t(160 * 1024 - 256 - 24 * 1024) / int64_t(fix_row))));
   // rider slots ~ the rows sweep 2 queues: bf16 ~0.4 % of them, fp16 ~3.7 % (its T ulp is 2^13 fp32 ulps); a rider wave
   // that finds more entries than slots takes several in turn
   const int64_t want_slots = cs.strict == 2 ? 8192 : std::max<int64_t>(64, p.dt == VC2_F16 ? p.R / 24 : p.R / 128);
@@ -4814,7 +4480,7 @@ int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, boo
                        (cs.strict && !fused) ? wsp<int>(ws, p.o_ticket) + kTkCorrCount : (int*)nullptr,
                        wsp<NormCorr>(ws, p.o_corr), cs.strict, wsp<int>(ws, p.o_vticket), fs,
                        margin_depth(p.N, cs.strict), (!single_rank && cs.strict == 3) ? 1 : 0, wsp<float>(ws, p.o_dmin),
-                       (own_stats && cs.strict == 4 && !ord) ? double(VC2_FRAME_A) : 0.0, wsp<uint32_t>(ws, p.o_rlist), rcap, fr,
+                       (own_stats && cs.strict == 4 && !ord) ? kFrameA : 0.0, wsp<uint32_t>(ws, p.o_rlist), rcap, fr,
                        OrdSrc{ord ? wsp<float>(ws, p.o_bsum) : (const float*)nullptr, ord ? 1 : 0, ord ? p.ord_nA : 0});
   };
   if (!fused) {
@@ -4834,16 +4500,15 @@ int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, boo
   const FrameReplay frp{wsp<uint32_t>(ws, p.o_rlist), wsp<int>(ws, p.o_ticket) + kTkFrameReplays, rcap,
                         wsp<float>(ws, p.o_fc), int(p.N),
                         FrameFix{part, ord ? p.ord_S : p.S, p.S_q, cs.strict, margin_depth(p.N, cs.strict),
-                                 (own_stats && cs.strict == 4) ? double(VC2_FRAME_A) : 0.0, fs,
+                                 (own_stats && cs.strict == 4) ? kFrameA : 0.0, fs,
                                  wsp<int>(ws, p.o_ticket) + kTkCorrCount, wsp<NormCorr>(ws, p.o_corr),
                                  OrdSrc{ord ? wsp<float>(ws, p.o_bsum) : (const float*)nullptr, ord ? 1 : 0, ord ? p.ord_nA : 0}},
                         fused ? wsp<uint32_t>(ws, p.o_rlist) + rcap : (const uint32_t*)nullptr,
                         wsp<int>(ws, p.o_ticket) + kTkFixEntries, rcap2,
                         fused ? wsp<int>(ws, p.o_fmark) : (const int*)nullptr};
-  static const int env_rw = [] { const char* e = getenv("VC2_REPLAY_WAVES"); return e ? atoi(e) : 0; }();
   // rider waves (debug mode 2 replays every mean; fp16 lists ~8x bf16's).  ORD: no mean is replayed -- the riders only redo the
   // frames that hold a row with a corrected norm (one entry per block of 64 columns: bf16 ~2 frames per pass, fp16 ~16)
-  const int rwaves = env_rw > 0 ? env_rw : ord ? (p.dt == VC2_F16 ? 1024 : 256) : cs.strict == 2 ? 8192 : (p.dt == VC2_F16 ? 4096 : 1024);
+  const int rwaves = ord ? (p.dt == VC2_F16 ? 1024 : 256) : cs.strict == 2 ? 8192 : (p.dt == VC2_F16 ? 4096 : 1024);
   if (single_rank) {
     const int lpv = cascade_lp(p.R);
     const int G1v = int(cdiv(p.R >> lpv, int64_t(1) << lpv));
@@ -5457,22 +5122,20 @@ int vc2_compress_ex2(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   int* const status = wsp<int>(ws, p.o_ticket) + kTkStatus;       // the pass's status word (-> K_out[1])
   // the variance reduction and the channel selection in ONE launch (k_var_select): 16-bit inputs, D <= 4096, this pass ran its
   // own sweep 1 (which left the variance array at "not written yet"), no per-kernel timing.  VC2_VARSEL=0: two launches
-  const int varsel_env = [] { const char* e = getenv("VC2_VARSEL"); return e ? atoi(e) : 1; }();          // (read per pass, like VC2_S2_ORD)
-  const int sel4_env2 = [] { const char* e = getenv("VC2_SEL4"); const char* e3 = getenv("VC2_SEL3"); return (e ? atoi(e) : 1) != 0 && !(e3 && atoi(e3) != 0); }();
   // (the selection workgroup WAITS inside the launch for the variance workgroups: they must be able to run beside it -- a
   //  device with a handful of CUs keeps the two launches; a stream whose CU mask leaves one CU must set VC2_VARSEL=0: the bounded
   //  wait would expire, and the pass would report status bit 2 instead of hanging)
   static const int n_cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev);
                                 if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); n = 0; }
                                 return n; }();
-  if (varsel_env != 0 && n_cus >= 16 && sel4_env2 && p.ES == 2 && D <= 4096 && !(flags & VC2_FLAG_HAVE_STATS) && !g_prof && kc > 0 && kc < D) {
+  if (test_seam_on("VC2_VARSEL") && n_cus >= 16 && test_seam_on("VC2_SEL4") && p.ES == 2 && D <= 4096 && !(flags & VC2_FLAG_HAVE_STATS) && !g_prof && kc > 0 && kc < D) {
     if ((rc = launch_stats_sweep(p, x, ws, PoolSrc{}, st, reinterpret_cast<uint32_t*>(var_f32)))) return rc;
     const int64_t n_each = int64_t(p.BF) * p.N, n_last = p.R - int64_t(p.NB - 1) * n_each;
     VarSelArgs va{p.NB, n_each, n_last, int(D), var_f32, wsp<int>(ws, p.o_ticket),
                   PartSrc{wsp<double>(ws, p.o_part_stats), x, p.R, p.BF * p.stat_splits, p.G, int(p.N), p.BF},
                   make_fold_tab(p.NB, n_each, n_last), wsp<unsigned long long>(ws, p.o_nfixlist), int(p.R + cdiv(p.F, 2)),
                   reinterpret_cast<unsigned long long*>(K_out + 1), int(kc), cols, perm, wperm, wcpos, status,
-                  [] { const char* e = getenv("VC2_CODE_WARM"); const int v = e ? atoi(e) : 88; return v < 0 ? 0 : (v > 88 ? 88 : v) * 1024; }()};
+                  kCodeWarmBytes};
     const size_t smem = chan_select_lds(int(D));
     const unsigned nvb = unsigned(cdiv(D, 16));                    // workgroups of the variance reduction
     auto go = [&](auto kernel) -> int {
@@ -5672,7 +5335,7 @@ int vc2_profile_collect(int max_kernels, const char** names, double* total_ms, i
   return n;
 }
 
-#ifdef VC2_DEBUG_EXPORTS     // (scripts/dev/*: where a plan keeps its arrays, run-time switches of kernel variants)
+#ifdef VC2_DEBUG_EXPORTS     // (scripts/dev/*: where a plan keeps its arrays)
 int vc2_debug_plan(int64_t F, int64_t N, int64_t D, int dtype, int64_t* out /*[16]*/) {
   Plan p;
   int rc = make_plan(F, N, D, dtype, &p);
@@ -5680,11 +5343,6 @@ int vc2_debug_plan(int64_t F, int64_t N, int64_t D, int dtype, int64_t* out /*[1
   const int64_t v[16] = {int64_t(p.o_den), int64_t(p.o_part_col), int64_t(p.o_rflag), int64_t(p.o_ticket), int64_t(p.o_nfixlist),
                          p.S, p.S_q, p.S_W, int64_t(p.o_fc), int64_t(p.o_vc), int64_t(p.o_total), int64_t(p.o_cols), p.S2, int64_t(p.o_vpart), 0, 0};
   for (int i = 0; i < 16; ++i) out[i] = v[i];
-  return VC2_OK;
-}
-int vc2_debug_set(int key, int value) {
-  if (key == 0) g_s2v2.store(value, std::memory_order_relaxed);
-  if (key == 1) g_s3v2.store(value, std::memory_order_relaxed);
   return VC2_OK;
 }
 #endif
