@@ -238,6 +238,43 @@ int vc2_keep_positions(const uint8_t* video_mask, int64_t S, const int64_t* kept
                        const uint8_t* visual_mask, int64_t* keep_out, int64_t keep_cap, int64_t* vis_rows_out,
                        int64_t vis_cap, int64_t* counts_out, void* stream);
 
+/* ---- batched prefill pruning (B > 1 prompts of a padded batch) ---------------------------------------------------
+ * Each entry batches the per-row operation of models/qwen2_5_vl.py:156-183 (keep every non-video position of a row plus
+ * its kept video tokens, slice the prompt tensors to them) and re-pads the pruned rows, which now differ in length.
+ *
+ * vc2_keep_positions_batched: video_mask uint8[B, S]; kept[K] = the batch's kept video ordinals, strictly ascending over
+ * the video positions of the whole batch in row-major order (the order of HF's video mask and of video_grid_thw).  Row b
+ * keeps its n_b = S - (video positions of b) + (kept ordinals in b) positions; S' = max n_b.  Outputs, written with row
+ * length S' (capacity: B * S_cap entries for keep_out / mask_out, R * B * S_cap for pos_out):
+ *   keep_out int64[B, S']    kept positions of row b in order at slots [off_b, off_b + n_b), -1 in the other slots
+ *                            (pad slots); off_b = S' - n_b when pad_left, else 0
+ *   lengths_out int64[B]     n_b
+ *   vis_rows_out (optional, needs visual_mask uint8[B, S])  ordinals, among the flattened visual positions of the batch,
+ *                            of the kept ones (the rows Qwen3-VL's deep-stack tensors keep); at most vis_cap
+ *   mask_out (optional, needs attention_mask int64[B, S])  attention_mask gathered at keep_out, 0 in pad slots
+ *                            (attention_mask NULL: 1 in the kept slots)
+ *   pos_out (optional, needs pos int64[R, B, S], R <= 4)  every plane gathered at keep_out; a pad slot holds the plane's
+ *                            value at the row's first existing pad slot (attention_mask == 0), 0 when the row has none.
+ *                            text_row0: plane 0 holds text positions instead -- in a kept slot with attention_mask != 0
+ *                            its rank among those slots of the row (0, 1, ...), in the other slots the pad value.
+ * row_ws: device scratch of 4 * B int64.  counts_out (optional; device memory, or pinned host memory that is then stored
+ * system-scope, the error word last, for a host spinning on counts_out[2] preset to -1) = {S', kept visual rows, error
+ * bits}: 1 = S' > S_cap, 2 = more visual rows than vis_cap, 4 = kept[] not strictly ascending inside [0, video positions
+ * of the batch), 8 = the batch's video positions differ from n_video (n_video < 0: not checked), 16 = a video position
+ * the visual mask does not flag.  On any error nothing but lengths_out (zeros) and counts_out is written.
+ * Two launches (per-row statistics, then the rows), no host round trip.  B <= 256, S <= 983 040.
+ *
+ * vc2_repad_rows: dst[b, j, :] = src[b, keep[b, j], :] for src T[B, S, D], keep int64[B, Sp] (vc2_keep_positions_batched's
+ * keep_out), dst T[B, Sp, D]; a zero row where keep[b, j] < 0.  An entry >= S is not read: its row is zeroed and
+ * status (optional device word) |= 2. */
+int vc2_keep_positions_batched(const uint8_t* video_mask, int64_t B, int64_t S, const int64_t* kept, int64_t K,
+                               int64_t n_video, int pad_left, const uint8_t* visual_mask, const int64_t* attention_mask,
+                               const int64_t* pos, int64_t R, int text_row0, int64_t* keep_out, int64_t* lengths_out,
+                               int64_t S_cap, int64_t* vis_rows_out, int64_t vis_cap, int64_t* mask_out, int64_t* pos_out,
+                               int64_t* row_ws, int64_t* counts_out, void* stream);
+int vc2_repad_rows(const void* src, int64_t B, int64_t S, int64_t D, int dtype, const int64_t* keep, int64_t Sp, void* dst,
+                   int32_t* status, void* stream);
+
 /* ---- frame-sharded multi-GPU building blocks -------------------------
  * A rank holds frames [f0, f0+F_local) of a video with F_total frames.  Between the local sweeps the Python
  * layer all-gathers three small fp64 / fp32 arrays over RCCL.  Exchanges 1 and 2 carry CANONICAL partials -- per

@@ -46,6 +46,9 @@ _SIGNATURES = {
     "vc2_pool_stats": [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp],
     "vc2_gather_scatter": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "vc2_keep_positions": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
+    "vc2_keep_positions_batched": [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64,
+                                   _vp, _i64, _vp, _vp, _vp, _vp, _vp],
+    "vc2_repad_rows": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
     "vc2_stat_block_frames": [],
     "vc2_chan_stats": [_vp, _i64, _i64, _i64, _i32, _i64, _i32, _vp, _sz, _vp, _vp],
     "vc2_chan_var_from_stats": [_vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp],

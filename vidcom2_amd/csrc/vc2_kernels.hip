@@ -3957,6 +3957,245 @@ __global__ __launch_bounds__(kKeepNT) void k_keep_positions(const uint8_t* __res
   }
 }
 
+// ---- batched prefill pruning (hooks, B > 1): the per-row operation of models/qwen2_5_vl.py:156-183 over a padded batch
+// k_keep_rowstats: one workgroup per row of video_mask [B, S]: its video / visual positions, its first pad slot (the first
+// attention_mask == 0, S when there is none) and the row's error bits; the workgroups also check, between them, that
+// kept[] ascends strictly from 0.  -> row_ws[b] = {video positions, visual positions, first pad slot, error bits}.
+// k_keep_batched: one workgroup per row again; every workgroup first folds all rows' words into the batch's S' = max n_b
+// (n_b = S - video positions of row b + kept ordinals that fall into row b: two binary searches per row over kept[]), then
+// puts the row's kept ordinals into an LDS bitmap (as k_keep_positions does) and writes the row's kept positions at
+// slots [off_b, off_b + n_b) of keep_out[b, 0 .. S'), off_b = S' - n_b on the left-padded side, 0 on the right.
+constexpr int kKbNT = 1024;
+constexpr int64_t kKbMaxRows = 256;             // rows of a batch (the fold's LDS tables)
+__global__ __launch_bounds__(kKbNT) void k_keep_rowstats(const uint8_t* __restrict__ video_mask, int64_t S,
+                                                         const uint8_t* __restrict__ visual_mask,
+                                                         const int64_t* __restrict__ attn, const int64_t* __restrict__ kept,
+                                                         int64_t K, int64_t* __restrict__ row_ws) {
+  __shared__ uint32_t xch[16];
+  __shared__ unsigned long long first_pad;
+  __shared__ int err_s;
+  constexpr int NW = kKbNT / 64;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  if (tid == 0) { first_pad = (unsigned long long)S; err_s = 0; }
+  __syncthreads();
+  const uint8_t* vm = video_mask + b * S;
+  const uint8_t* vs = visual_mask ? visual_mask + b * S : nullptr;
+  const int64_t E = (S + kKbNT - 1) / kKbNT;
+  const int64_t p0 = min(S, tid * E), p1 = min(S, p0 + E);
+  uint32_t nv = 0, nvis = 0;
+  int bad = 0;
+  keep_walk(vm, vs, p0, p1, [&](int64_t, bool vid, bool vis) {
+    nv += vid ? 1u : 0u;
+    nvis += vis ? 1u : 0u;
+    if (vs && vid && !vis) bad = 16;                             // a video token the visual mask does not flag
+  });
+  if (attn) {
+    const int64_t* am = attn + b * S;
+    for (int64_t p = p0; p < p1; ++p)
+      if (am[p] == 0) { atomicMin(&first_pad, (unsigned long long)p); break; }
+  }
+  // kept[] strictly ascending from 0 (its upper end is checked against the batch's video positions in k_keep_batched)
+  for (int64_t i = b * kKbNT + tid; i < K; i += int64_t(gridDim.x) * kKbNT) {
+    const int64_t v = kept[i];
+    if (v < 0 || (i + 1 < K && kept[i + 1] <= v)) bad |= 4;
+  }
+  if (bad) atomicOr(&err_s, bad);
+  uint32_t tv, tvis;
+  block_excl_scan<NW>(nv, xch, tv);
+  __syncthreads();
+  block_excl_scan<NW>(nvis, xch, tvis);
+  __syncthreads();
+  if (tid == 0) {
+    row_ws[4 * b] = tv;
+    row_ws[4 * b + 1] = tvis;
+    row_ws[4 * b + 2] = (int64_t)first_pad;
+    row_ws[4 * b + 3] = err_s;
+  }
+}
+
+struct KbArgs {
+  const uint8_t* video_mask; const uint8_t* visual_mask; const int64_t* attn; const int64_t* pos;
+  int64_t B, S, R; const int64_t* kept; int64_t K; int64_t n_video; int pad_left, text_row0;
+  int64_t* keep_out; int64_t* lengths_out; int64_t S_cap; int64_t* vis_rows_out; int64_t vis_cap;
+  int64_t* mask_out; int64_t* pos_out; const int64_t* row_ws; int64_t* counts_out;
+};
+__device__ __forceinline__ int64_t lower_bound_i64(const int64_t* __restrict__ a, int64_t n, int64_t v) {
+  int64_t lo = 0, hi = n;
+  while (lo < hi) { const int64_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
+  return lo;
+}
+__global__ __launch_bounds__(kKbNT) void k_keep_batched(KbArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t bitmap[];     // [ceil(video positions of the row / 32)]
+  __shared__ uint32_t xch[16];
+  __shared__ int64_t sh_nb[kKbMaxRows], sh_ord0[kKbMaxRows], sh_lo[kKbMaxRows], sh_vis0[kKbMaxRows], sh_visb[kKbMaxRows];
+  __shared__ int64_t sh_Sp, sh_tot_vis;
+  __shared__ int sh_err;
+  constexpr int NW = kKbNT / 64;
+  const int tid = threadIdx.x;
+  const int64_t b = blockIdx.x, B = a.B, S = a.S;
+  // ---- the batch's geometry, from every row's words (B <= kKbMaxRows; thread 0 folds, the rows are few)
+  if (tid == 0) {
+    int err = 0;
+    int64_t ord = 0;
+    for (int64_t r = 0; r < B; ++r) { sh_ord0[r] = ord; ord += a.row_ws[4 * r]; err |= int(a.row_ws[4 * r + 3]); }
+    if (a.K > 0 && a.kept[a.K - 1] >= ord) err |= 4;               // (kept ascends: its last entry bounds them all)
+    if (a.n_video >= 0 && ord != a.n_video) err |= 8;
+    int64_t Sp = 0, vis = 0, visb = 0;
+    for (int64_t r = 0; r < B; ++r) {
+      const int64_t nvid = a.row_ws[4 * r];
+      const int64_t lo = lower_bound_i64(a.kept, a.K, sh_ord0[r]), hi = lower_bound_i64(a.kept, a.K, sh_ord0[r] + nvid);
+      sh_lo[r] = lo;
+      sh_nb[r] = S - nvid + (hi - lo);
+      Sp = max(Sp, sh_nb[r]);
+      sh_vis0[r] = vis; sh_visb[r] = visb;
+      vis += a.row_ws[4 * r + 1] - nvid + (hi - lo);                // (video tokens are visual tokens: bit 16 otherwise)
+      visb += a.row_ws[4 * r + 1];
+    }
+    if (Sp > a.S_cap) err |= 1;
+    if (a.vis_rows_out && vis > a.vis_cap) err |= 2;
+    sh_Sp = Sp; sh_tot_vis = a.visual_mask ? vis : 0; sh_err = err;
+  }
+  __syncthreads();
+  const int err = sh_err;
+  const int64_t Sp = sh_Sp;
+  if (err == 0) {
+    const int64_t nb = sh_nb[b], ord0 = sh_ord0[b], nvid = a.row_ws[4 * b], lo = sh_lo[b];
+    const int64_t off = a.pad_left ? Sp - nb : 0;
+    const int64_t fpad = a.row_ws[4 * b + 2];
+    const uint8_t* vm = a.video_mask + b * S;
+    const uint8_t* vs = a.visual_mask ? a.visual_mask + b * S : nullptr;
+    const int64_t* am = a.attn ? a.attn + b * S : nullptr;
+    for (int64_t w = tid; w < (nvid + 31) / 32; w += kKbNT) bitmap[w] = 0u;
+    __syncthreads();
+    for (int64_t i = lo + tid; i < a.K && a.kept[i] < ord0 + nvid; i += kKbNT) {
+      const int64_t o = a.kept[i] - ord0;
+      atomicOr(&bitmap[o >> 5], 1u << (o & 31));
+    }
+    __syncthreads();
+    const int64_t E = (S + kKbNT - 1) / kKbNT;
+    const int64_t p0 = min(S, tid * E), p1 = min(S, p0 + E);
+    // pass 1: my video tokens (-> ordinal of my first), kept positions, kept valid positions (text ranks), visual
+    // positions and kept visual positions
+    uint32_t nv = 0;
+    keep_walk(vm, vm, p0, p1, [&](int64_t, bool vid, bool) { nv += vid ? 1u : 0u; });
+    uint32_t tot;
+    const int64_t vo0 = block_excl_scan<NW>(nv, xch, tot);
+    __syncthreads();
+    uint32_t nk = 0, nval = 0, nvis = 0, nvk = 0;
+    {
+      int64_t o = vo0;
+      keep_walk(vm, vs, p0, p1, [&](int64_t p, bool vid, bool vis) {
+        bool keep = true;
+        if (vid) { keep = (bitmap[o >> 5] >> (o & 31)) & 1u; ++o; }
+        nk += keep ? 1u : 0u;
+        nval += (keep && (!am || am[p] != 0)) ? 1u : 0u;
+        if (vis) { ++nvis; nvk += keep ? 1u : 0u; }
+      });
+    }
+    const int64_t k0 = block_excl_scan<NW>(nk, xch, tot);
+    __syncthreads();
+    const int64_t t0 = block_excl_scan<NW>(nval, xch, tot);
+    __syncthreads();
+    const int64_t v0 = block_excl_scan<NW>(nvis, xch, tot);
+    __syncthreads();
+    const int64_t vk0 = block_excl_scan<NW>(nvk, xch, tot);
+    __syncthreads();
+    int64_t* keep_row = a.keep_out + b * Sp;
+    // pad slots: keep -1, mask 0, every position plane the value of the row's first existing pad slot (0 without one)
+    for (int64_t j = tid; j < Sp - nb; j += kKbNT) {
+      const int64_t s = a.pad_left ? j : nb + j;
+      keep_row[s] = -1;
+      if (a.mask_out) a.mask_out[b * Sp + s] = 0;
+      if (a.pos_out)
+        for (int64_t r = 0; r < a.R; ++r)
+          a.pos_out[(r * B + b) * Sp + s] = fpad < S ? a.pos[(r * B + b) * S + fpad] : 0;
+    }
+    {
+      int64_t o = vo0, kk = off + k0, tt = t0, vv = sh_visb[b] + v0, vk = sh_vis0[b] + vk0;
+      keep_walk(vm, vs, p0, p1, [&](int64_t p, bool vid, bool vis) {
+        bool keep = true;
+        if (vid) { keep = (bitmap[o >> 5] >> (o & 31)) & 1u; ++o; }
+        if (keep) {
+          keep_row[kk] = p;
+          const bool valid = !am || am[p] != 0;
+          if (a.mask_out) a.mask_out[b * Sp + kk] = am ? am[p] : 1;
+          if (a.pos_out) {
+            for (int64_t r = 0; r < a.R; ++r) {
+              int64_t v = a.pos[(r * B + b) * S + p];
+              if (r == 0 && a.text_row0) v = valid ? tt : (fpad < S ? a.pos[b * S + fpad] : 0);
+              a.pos_out[(r * B + b) * Sp + kk] = v;
+            }
+          }
+          tt += valid ? 1 : 0;
+          ++kk;
+        }
+        if (vis) { if (keep && a.vis_rows_out) a.vis_rows_out[vk++] = vv; ++vv; }
+      });
+    }
+    if (tid == 0) a.lengths_out[b] = nb;
+  } else if (tid == 0) {
+    a.lengths_out[b] = 0;
+  }
+  if (b == 0 && tid == 0 && a.counts_out) {
+    long long* co = reinterpret_cast<long long*>(a.counts_out);
+    __hip_atomic_store(co, (long long)Sp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(co + 1, (long long)sh_tot_vis, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+    __hip_atomic_store(co + 2, (long long)err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);   // (last: what the host waits for)
+  }
+}
+
+// Re-padding row gather (the memory-bound half of a batched pruned prefill): dst[b, j] = src[b, keep[b, j]] for
+// src T[B, S, D], keep int64[B, Sp], dst T[B, Sp, D]; a zero row where keep[b, j] < 0 (a pad slot).  One WAVE per row,
+// every lane's share of the row (up to 8 x 16 B) loaded before any of it is stored, four rows per workgroup and a grid of
+// up to 4096 workgroups: ~2 k rows in flight.  A keep entry >= S is reported (status |= 2) and its row zeroed.
+constexpr int kRepadNT = 256;
+constexpr int kRepadU = 8;
+__global__ __launch_bounds__(kRepadNT) void k_repad_rows(const unsigned char* __restrict__ src, int64_t S,
+                                                        const int64_t* __restrict__ keep, int64_t rows, int64_t Sp,
+                                                        int64_t row_bytes, unsigned char* __restrict__ dst,
+                                                        int* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const int64_t nwaves = int64_t(gridDim.x) * (kRepadNT / 64);
+  const bool vec = (row_bytes & 15) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
+  for (int64_t r = int64_t(blockIdx.x) * (kRepadNT / 64) + (threadIdx.x >> 6); r < rows; r += nwaves) {
+    const int64_t b = r / Sp;
+    int64_t k = keep[r];
+    if (k >= S) { if (lane == 0 && status) atomicOr(status, 2); k = -1; }
+    unsigned char* d = dst + r * row_bytes;
+    const unsigned char* s = k >= 0 ? src + (b * S + k) * row_bytes : nullptr;
+    if (vec) {
+      const int64_t nv = row_bytes >> 4;
+      uint4* dv = reinterpret_cast<uint4*>(d);
+      const uint4* sv = reinterpret_cast<const uint4*>(s);
+      for (int64_t t0 = 0; t0 < nv; t0 += 64 * kRepadU) {
+        uint4 v[kRepadU];
+#pragma unroll
+        for (int u = 0; u < kRepadU; ++u) {
+          const int64_t t = t0 + u * 64 + lane;
+          v[u] = (s && t < nv) ? sv[t] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < kRepadU; ++u) {
+          const int64_t t = t0 + u * 64 + lane;
+          if (t < nv) {
+            uint32_t* dw = reinterpret_cast<uint32_t*>(dv + t);
+            __builtin_nontemporal_store(v[u].x, dw);
+            __builtin_nontemporal_store(v[u].y, dw + 1);
+            __builtin_nontemporal_store(v[u].z, dw + 2);
+            __builtin_nontemporal_store(v[u].w, dw + 3);
+          }
+        }
+      }
+    } else {                                                       // (rows of 2-byte multiples: odd D, unaligned views)
+      const int64_t nh = row_bytes >> 1;
+      for (int64_t t = lane; t < nh; t += 64)
+        reinterpret_cast<uint16_t*>(d)[t] = s ? reinterpret_cast<const uint16_t*>(s)[t] : uint16_t(0);
+    }
+  }
+}
+
 // ---- known-answer-test kernels -------------------------------------------------------
 template <int DT>
 __global__ void k_kat_exp(const void* __restrict__ in, int64_t n, void* __restrict__ out) {
@@ -5043,6 +5282,52 @@ int vc2_keep_positions(const uint8_t* video_mask, int64_t S, const int64_t* kept
                                                                                                  : go(k_keep_positions<0>);
   if (rcg) return rcg;
   return check_launch("keep_positions");
+}
+
+int vc2_keep_positions_batched(const uint8_t* video_mask, int64_t B, int64_t S, const int64_t* kept, int64_t K,
+                               int64_t n_video, int pad_left, const uint8_t* visual_mask, const int64_t* attention_mask,
+                               const int64_t* pos, int64_t R, int text_row0, int64_t* keep_out, int64_t* lengths_out,
+                               int64_t S_cap, int64_t* vis_rows_out, int64_t vis_cap, int64_t* mask_out, int64_t* pos_out,
+                               int64_t* row_ws, int64_t* counts_out, void* stream) {
+  if (!video_mask || B <= 0 || S <= 0 || K < 0 || (K > 0 && !kept) || !keep_out || !lengths_out || !row_ws || S_cap < 0 ||
+      vis_cap < 0 || (vis_rows_out && !visual_mask) || (pos_out && (!pos || R <= 0 || R > 4)))
+    return fail(VC2_ERR_ARG, "bad keep_positions_batched arguments");
+  if (B > kKbMaxRows) return fail(VC2_ERR_UNSUPPORTED, "B=%lld rows (at most %lld)", (long long)B, (long long)kKbMaxRows);
+  if (S > kKeepBitmapMaxS) return fail(VC2_ERR_UNSUPPORTED, "S=%lld positions per row (at most %lld)", (long long)S,
+                                       (long long)kKeepBitmapMaxS);
+  if (counts_out) {       // pinned host memory: its device alias (as vc2_keep_positions)
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, counts_out) == hipSuccess) {
+      if (at.type == hipMemoryTypeHost && at.devicePointer) counts_out = static_cast<int64_t*>(at.devicePointer);
+    } else {
+      (void)hipGetLastError();
+    }
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_keep_rowstats, dim3(unsigned(B)), dim3(kKbNT), 0, st, video_mask, S, visual_mask, attention_mask,
+                     kept, K, row_ws);
+  if (int rc = check_launch("keep_rowstats")) return rc;
+  KbArgs a{video_mask, visual_mask, attention_mask, pos_out ? pos : nullptr, B, S, pos_out ? R : 0, kept, K, n_video,
+           pad_left ? 1 : 0, text_row0 ? 1 : 0, keep_out, lengths_out, S_cap, vis_rows_out, vis_rows_out ? vis_cap : 0,
+           mask_out, pos_out, row_ws, counts_out};
+  const size_t smem = size_t((S + 31) / 32) * 4 + 16;
+  const size_t static_lds = size_t(5 * kKbMaxRows + 2) * 8 + 16 * 4 + 16;
+  if (int rca = allow_big_lds(&k_keep_batched, smem, "k_keep_batched", static_lds)) return rca;
+  hipLaunchKernelGGL(k_keep_batched, dim3(unsigned(B)), dim3(kKbNT), smem, st, a);
+  return check_launch("keep_batched");
+}
+
+int vc2_repad_rows(const void* src, int64_t B, int64_t S, int64_t D, int dtype, const int64_t* keep, int64_t Sp, void* dst,
+                   int32_t* status, void* stream) {
+  if (!src || !keep || !dst || B <= 0 || S <= 0 || D <= 0 || Sp < 0 || dtype < 0 || dtype > 2)
+    return fail(VC2_ERR_ARG, "bad repad_rows arguments");
+  const int64_t rows = B * Sp;
+  if (rows == 0) return VC2_OK;
+  const unsigned grid = unsigned(std::min<int64_t>(cdiv(rows, kRepadNT / 64), 4096));
+  hipLaunchKernelGGL(k_repad_rows, dim3(grid), dim3(kRepadNT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned char*>(src), S, keep, rows, Sp, D * (dtype == VC2_F32 ? 4 : 2),
+                     static_cast<unsigned char*>(dst), status);
+  return check_launch("repad_rows");
 }
 
 int vc2_gather_rows(const void* src, int64_t src_rows, int64_t D, int dtype, const int64_t* idx,

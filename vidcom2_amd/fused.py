@@ -9,6 +9,9 @@ Host mirror of `vc2_gather_scatter` / `vc2_keep_positions` (include/vc2.h).  The
   sequence positions on the device (no `nonzero` round trips), `gather_scatter` copies text and kept video rows in
   one launch;
 * the N+1 gathers of Qwen3-VL's deep-stack (models/qwen3_vl.py:140-165): several tensors, one index list, one launch;
+* the same slicing for a padded batch of B > 1 prompts (the hooks' batched prefill): `keep_positions_batched` builds
+  every row's kept positions, the pruned attention mask and position planes, `repad_rows` gathers the rows re-padded to
+  the longest pruned prompt;
 * (f3) LLaVA's `get_2dPool` (llava/model/llava_arch.py:171-190) followed by the pass's first sweep: `pool_stats`
   writes the pooled video once and leaves its channel statistics in the pass's workspace.
 
@@ -18,7 +21,7 @@ from __future__ import annotations
 
 import ctypes
 import threading
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -26,7 +29,7 @@ from ._ffi import DTYPE_CODE, check, lib, on_device, ptr, require_device, stream
 
 _check_rc = check          # (gather_scatter has a keyword argument named `check`)
 
-__all__ = ["gather_scatter", "keep_positions", "pool_stats", "POOL_MODES"]
+__all__ = ["gather_scatter", "keep_positions", "keep_positions_batched", "repad_rows", "pool_stats", "POOL_MODES"]
 
 MAX_SOURCES = 8
 
@@ -180,6 +183,127 @@ def keep_positions(video_mask: torch.Tensor, kept: torch.Tensor, n_video: Option
             raise IndexError(f"keep_positions: visual_mask flags {found_vis + int(n_video) - K} positions, the caller said {n_visual}")
         vis_rows = vis_rows[:found_vis]
     return keep, vis_rows
+
+
+class BatchedKeep(NamedTuple):
+    """What `keep_positions_batched` returns (device tensors; rows re-padded to S' = max(lengths))."""
+    keep: torch.Tensor                      # int64 [B, S'], kept positions of each row, -1 in pad slots
+    lengths: torch.Tensor                   # int64 [B]
+    S: int                                  # S'
+    vis_rows: Optional[torch.Tensor]        # int64 [kept visual rows] (visual_mask given)
+    mask: Optional[torch.Tensor]            # int64 [B, S'] (attention_mask given)
+    pos: Optional[torch.Tensor]             # int64 [R, B, S'] (position_ids given)
+
+
+def _u8(t: torch.Tensor) -> torch.Tensor:
+    return (t.view(torch.uint8) if t.dtype == torch.bool else (t != 0).to(torch.uint8)).contiguous()
+
+
+def keep_positions_batched(video_mask: torch.Tensor, kept: torch.Tensor, n_video: Optional[int] = None,
+                           pad_left: bool = True, visual_mask: Optional[torch.Tensor] = None,
+                           attention_mask: Optional[torch.Tensor] = None, position_ids: Optional[torch.Tensor] = None,
+                           text_row0: bool = False, n_visual: Optional[int] = None) -> BatchedKeep:
+    """`keep_positions` for a padded batch (vc2_keep_positions_batched, include/vc2.h): row b keeps every non-video
+    position plus its video tokens whose ordinal -- counted over the whole batch's video positions in row-major order --
+    is in `kept` (sorted int64); the rows are re-padded on the left (`pad_left`) or the right to the longest one.
+    attention_mask [B, S] / position_ids [R, B, S] (R <= 4) come back gathered at the kept positions, pad slots masked and
+    holding the row's pad position value (include/vc2.h); text_row0: plane 0 of position_ids carries text positions
+    (0, 1, ... over the row's unmasked kept slots).  n_video / n_visual = the True entries of video_mask / visual_mask
+    (the rows of the video embeds / deep-stack tensors), checked on the device.  One host wait (for S')."""
+    if video_mask.dim() != 2:
+        raise RuntimeError(f"video_mask must be [B, S], got {tuple(video_mask.shape)}")
+    vm = _u8(video_mask)
+    require_device(vm, "video_mask")
+    B, S = (int(v) for v in vm.shape)
+    kept = kept.to(device=vm.device, dtype=torch.int64).contiguous()
+    K = int(kept.numel())
+    dev = vm.device
+    vis = am = pos = None
+    if visual_mask is not None:
+        if tuple(visual_mask.shape) != (B, S) or visual_mask.device != dev:
+            raise RuntimeError("visual_mask must cover the same positions as video_mask")
+        vis = _u8(visual_mask)
+    if attention_mask is not None:
+        if tuple(attention_mask.shape) != (B, S) or attention_mask.device != dev:
+            raise RuntimeError(f"attention_mask must be a [{B}, {S}] tensor on {dev}")
+        am = attention_mask.to(torch.int64).contiguous()
+    R = 0
+    if position_ids is not None:
+        if position_ids.dim() != 3 or tuple(position_ids.shape[1:]) != (B, S) or not 1 <= position_ids.shape[0] <= 4 \
+                or position_ids.device != dev:
+            raise RuntimeError(f"position_ids must be an [R <= 4, {B}, {S}] tensor on {dev}")
+        pos = position_ids.to(torch.int64).contiguous()
+        R = int(pos.shape[0])
+    keep = torch.empty(B * S, dtype=torch.int64, device=dev)
+    lengths = torch.empty(B, dtype=torch.int64, device=dev)
+    vis_rows = torch.empty(int(vis.sum().item()) if n_visual is None else int(n_visual), dtype=torch.int64,
+                           device=dev) if vis is not None else None
+    mask = torch.empty(B * S, dtype=torch.int64, device=dev) if am is not None else None
+    pos_out = torch.empty(R * B * S, dtype=torch.int64, device=dev) if pos is not None else None
+    row_ws = torch.empty(4 * B, dtype=torch.int64, device=dev)
+    counts = _pinned_counts()
+    counts[2] = -1
+    with on_device(dev):
+        rc = lib().vc2_keep_positions_batched(ptr(vm), B, S, ptr(kept), K, -1 if n_video is None else int(n_video),
+                                              int(bool(pad_left)), ptr(vis), ptr(am), ptr(pos), R, int(bool(text_row0)),
+                                              ptr(keep), ptr(lengths), S, ptr(vis_rows),
+                                              vis_rows.numel() if vis_rows is not None else 0, ptr(mask), ptr(pos_out),
+                                              ptr(row_ws), ctypes.c_void_p(counts.data_ptr()), stream_ptr(dev))
+    check(rc, "vc2_keep_positions_batched")
+    if int(lib().vc2_wait_host_count(ctypes.c_void_p(counts.data_ptr() + 16), 0.05)) < 0:
+        torch.cuda.current_stream(dev).synchronize()             # (a busy stream: the plain wait)
+    Sp, found_vis, err = (int(v) for v in counts[:3].tolist())
+    if err:
+        why = []
+        if err & 1:
+            why.append(f"more kept positions than the capacity {S}")
+        if err & 2:
+            why.append("more kept visual rows than visual positions")
+        if err & 4:
+            why.append("kept must be strictly ascending ordinals of the batch's video positions")
+        if err & 8:
+            why.append(f"video_mask holds a different number of video positions than the caller's {n_video}")
+        if err & 16:
+            why.append("a video position is not flagged in visual_mask")
+        raise IndexError("keep_positions_batched: " + "; ".join(why))
+    return BatchedKeep(keep[:B * Sp].view(B, Sp), lengths, Sp,
+                       vis_rows[:found_vis] if vis_rows is not None else None,
+                       mask[:B * Sp].view(B, Sp) if mask is not None else None,
+                       pos_out[:R * B * Sp].view(R, B, Sp) if pos_out is not None else None)
+
+
+def repad_rows(src: torch.Tensor, keep: torch.Tensor, out: Optional[torch.Tensor] = None,
+               status: Optional[torch.Tensor] = None, check: bool = False) -> torch.Tensor:
+    """out[b, j] = src[b, keep[b, j]] for src [B, S, D] (fp32 / bf16 / fp16) and keep int64 [B, S'], a zero row where
+    keep[b, j] < 0 (vc2_repad_rows).  An entry >= S is not read: its row is zeroed and reported -- in `status` (device
+    int32[1], bit 1) and, check=True, by an IndexError after one small read-back.  The hooks pass the list
+    keep_positions_batched has just validated and skip that read-back."""
+    require_device(src, "src")
+    if src.dtype not in DTYPE_CODE:
+        raise TypeError(f"unsupported dtype {src.dtype} (fp32 / bf16 / fp16 only)")
+    if src.dim() != 3:
+        raise RuntimeError(f"src must be [B, S, D], got {tuple(src.shape)}")
+    B, S, D = (int(v) for v in src.shape)
+    if keep.dtype != torch.int64 or keep.device != src.device or keep.dim() != 2 or keep.shape[0] != B:
+        raise RuntimeError(f"keep must be an int64 [{B}, S'] tensor on {src.device}")
+    src = src if src.is_contiguous() else src.contiguous()
+    keep = keep.contiguous()
+    Sp = int(keep.shape[1])
+    if out is None:
+        out = torch.empty((B, Sp, D), dtype=src.dtype, device=src.device)
+    elif tuple(out.shape) != (B, Sp, D) or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise RuntimeError(f"out must be a contiguous [{B}, {Sp}, {D}] {src.dtype} tensor on {src.device}")
+    if check and status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=src.device)
+    if B * Sp == 0:
+        return out
+    with on_device(src.device):
+        rc = lib().vc2_repad_rows(ptr(src), B, S, D, DTYPE_CODE[src.dtype], ptr(keep), Sp, ptr(out), ptr(status),
+                                  stream_ptr(src.device))
+    _check_rc(rc, "vc2_repad_rows")
+    if check and int(status.item()) & 2:
+        raise IndexError(f"repad_rows: a keep entry is out of range for {S} positions per row")
+    return out
 
 
 POOL_MODES = {"average": 1, "max": 2, "bilinear": 3}

@@ -59,3 +59,9 @@ def retention_ratio() -> float:
 def compressor_enabled() -> bool:
     """`COMPRESSOR=vidcom2` env knob (models/qwen2_5_vl.py:121)."""
     return os.getenv("COMPRESSOR") == "vidcom2"
+
+
+def batched_prefill_enabled() -> bool:
+    """`VC2_BATCHED_PREFILL=1` env knob: the Qwen-VL hooks also prune video prefills of batch size > 1 (the reference
+    leaves those unpruned, models/qwen2_5_vl.py:120-130)."""
+    return os.getenv("VC2_BATCHED_PREFILL") == "1"

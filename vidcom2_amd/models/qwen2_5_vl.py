@@ -8,7 +8,8 @@ Behaviour kept from the reference:
 
 * active only when `COMPRESSOR=vidcom2`, the call carries `pixel_values_videos` + `video_grid_thw`,
   the KV cache is empty (prefill) and the batch size is 1 (qwen2_5_vl.py:120-129); otherwise the
-  model's own forward runs unchanged;
+  model's own forward runs unchanged -- except with `VC2_BATCHED_PREFILL=1`, which also prunes batches of
+  B > 1 prompts (every row exactly as the batch-1 hook prunes that prompt alone, re-padded; `_prefill_prune.py`);
 * every video is scored on its own (`_compute_keep_indices`, qwen2_5_vl.py:20-33, tokens per frame
   = h*w / merge_size**2), retention ratio from `R_RATIO`;
 * the prompt is cut down to text + kept video positions: `inputs_embeds`, `attention_mask`
@@ -26,11 +27,11 @@ import inspect
 import torch
 from torch import Tensor
 
-from ..vidcom2 import compress
+from ..vidcom2 import compress, compress_batch
 from ._intercept import compressor_enabled, original_method, retention_ratio
-from ._prefill_prune import run_with_pruning
+from ._prefill_prune import decode_state, run_decode_step, run_with_pruning
 
-__all__ = ["Qwen2_5_VLModel_forward", "_compute_keep_indices"]
+__all__ = ["Qwen2_5_VLModel_forward", "_compute_keep_indices", "_compute_keep_indices_many"]
 
 
 def _compute_keep_indices(flat_features: Tensor, grid_thw: Tensor, spatial_merge_size: int,
@@ -42,6 +43,31 @@ def _compute_keep_indices(flat_features: Tensor, grid_thw: Tensor, spatial_merge
     if frame_tokens <= 0 or flat_features.numel() == 0:
         return torch.arange(flat_features.shape[0], device=flat_features.device)
     return compress(flat_features, frame_tokens, base_scale, "linear", gather=False).global_idx
+
+
+def _compute_keep_indices_many(feats, grids, spatial_merge_size: int, base_scale: float) -> Tensor:
+    """The kept indices of several videos, as ONE ascending list over their concatenated tokens: the meaning of
+    `cat([_compute_keep_indices(f, g, ...) + offset_of_f for f, g in zip(feats, grids)])`.  On the device all the
+    videos run through `compress_batch` lanes (clips in flight, one host synchronisation for every count)."""
+    feats, kept, offsets, offset = list(feats), [], [], 0
+    jobs = []
+    for i, (f, g) in enumerate(zip(feats, grids)):
+        t, h, w = (int(v) for v in g.tolist())
+        frame_tokens = (h * w) // (spatial_merge_size ** 2)
+        offsets.append(offset)
+        kept.append(None)
+        if frame_tokens <= 0 or f.numel() == 0:
+            kept[i] = torch.arange(f.shape[0], device=f.device)
+        else:
+            jobs.append((i, frame_tokens))
+        offset += f.shape[0]
+    if jobs:
+        res = compress_batch([feats[i] for i, _ in jobs], [n for _, n in jobs], base_scale, gather=False)
+        for (i, _), r in zip(jobs, res):
+            kept[i] = r.global_idx
+    if not kept:
+        return torch.zeros(0, dtype=torch.int64)
+    return torch.cat([k + o for k, o in zip(kept, offsets)])
 
 
 def _cache_is_empty(past_key_values) -> bool:
@@ -67,8 +93,14 @@ def hooked_forward(self, hook, args, kwargs, keep_fn_name: str = "_compute_keep_
         bound = dict(kwargs)
     bound = {**bound.get("kwargs", {}), **bound}
     video_grid_thw = bound.get("video_grid_thw")
+    prefill = _cache_is_empty(bound.get("past_key_values"))
+    if prefill or not compressor_enabled():
+        decode_state(self, clear=True)          # (a batched pruned prefill's layout lives until the next prefill)
+    elif decode_state(self) is not None:
+        # a decode step behind a batched pruned prefill: the KV cache holds the PRUNED, re-padded prompt
+        return run_decode_step(self, lambda: original(*args, **kwargs))
     active = (compressor_enabled() and bound.get("pixel_values_videos") is not None
-              and video_grid_thw is not None and _cache_is_empty(bound.get("past_key_values")))
+              and video_grid_thw is not None and prefill)
     if not active:
         return original(*args, **kwargs)
 
@@ -79,7 +111,13 @@ def hooked_forward(self, hook, args, kwargs, keep_fn_name: str = "_compute_keep_
     def choose(video_embeds: Tensor):
         return _keep_per_video(video_embeds, video_grid_thw, merge_size, base_scale, keep_fn)
 
-    return run_with_pruning(self, lambda: original(*args, **kwargs), choose)
+    def choose_many(video_embeds: Tensor):
+        # B > 1: the same per-video scoring, all the batch's videos in flight at once (one host sync for the counts)
+        split_sizes = (video_grid_thw.prod(-1) // merge_size ** 2).tolist()
+        return globals()["_compute_keep_indices_many"](torch.split(video_embeds, split_sizes), video_grid_thw,
+                                                       merge_size, base_scale)
+
+    return run_with_pruning(self, lambda: original(*args, **kwargs), choose, choose_many=choose_many)
 
 
 def named_call_kwargs(self, hook, named: dict, extra: dict) -> dict:

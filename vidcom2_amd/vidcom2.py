@@ -489,6 +489,7 @@ def compress_batch(clips, tpf: int, base_scale: float = 0.25, in_flight: int = B
     replays; further clips in flight fill those gaps (DESIGN.md "clips in flight"; every lane keeps a plan = a workspace).
     Returns one CompressionResult per clip, in order.  The reference has no batched form: its harness loops
     over clips (lmms-eval, batch size 1 per rank).
+    `tpf` may also be a sequence of one tokens-per-frame value per clip (videos of different grids).
     Storage: for clips of ONE shape every result is a VIEW into batch-wide buffers (one allocation per output kind), so
     keeping any clip's rows / indices alive keeps the whole batch's buffers alive (n * capacity * D elements);
     own_storage=True hands every clip its own tensors instead (one extra device copy of the kept rows)."""
@@ -496,14 +497,22 @@ def compress_batch(clips, tpf: int, base_scale: float = 0.25, in_flight: int = B
     if not clips:
         return []
     dev = clips[0].device
-    for i, x in enumerate(clips):
-        if x.dim() != 2 or tpf <= 0 or x.shape[0] % int(tpf) != 0:
-            raise RuntimeError(f"clip {i}: shape {tuple(x.shape)} is not [frames * {tpf}, dim]")
+    if isinstance(tpf, (list, tuple)):
+        if len(tpf) != len(clips):
+            raise ValueError(f"{len(tpf)} tokens-per-frame values for {len(clips)} clips")
+        tpfs = [int(t) for t in tpf]
+    else:
+        tpfs = [int(tpf)] * len(clips)
+    for i, (x, t) in enumerate(zip(clips, tpfs)):
+        if x.dim() != 2 or t <= 0 or x.shape[0] % t != 0:
+            raise RuntimeError(f"clip {i}: shape {tuple(x.shape)} is not [frames * {t}, dim]")
     cur = torch.cuda.current_stream(dev)
     lanes = [cur] + _lane_streams(dev, max(1, min(int(in_flight), len(clips))) - 1)
-    same = all(c.shape == clips[0].shape and c.dtype == clips[0].dtype and c.device == dev for c in clips)
+    same = all(c.shape == clips[0].shape and c.dtype == clips[0].dtype and c.device == dev for c in clips) \
+        and all(t == tpfs[0] for t in tpfs)
     if not same:
-        return _compress_batch_mixed(clips, int(tpf), base_scale, lanes, gather)
+        return _compress_batch_mixed(clips, tpfs, base_scale, lanes, gather)
+    tpf = tpfs[0]
     # Clips of one shape (the batched-eval case, BASELINE config 5): ONE plan per lane (workspace; work on a stream is
     # ordered), ONE allocation per output kind for the whole batch -- each clip's pass writes its slice --, one
     # device-to-host copy for all the counts at the end.  Round 4 looked a plan up, allocated six tensors and recorded
@@ -544,8 +553,8 @@ def compress_batch(clips, tpf: int, base_scale: float = 0.25, in_flight: int = B
     return out
 
 
-def _compress_batch_mixed(clips, tpf: int, base_scale: float, lanes, gather: bool):
-    """compress_batch for clips of different shapes: a plan lookup and fresh outputs per clip."""
+def _compress_batch_mixed(clips, tpfs: List[int], base_scale: float, lanes, gather: bool):
+    """compress_batch for clips of different shapes (or tokens per frame): a plan lookup and fresh outputs per clip."""
     dev = clips[0].device
     cur = lanes[0]
     for st in lanes[1:]:
@@ -554,7 +563,7 @@ def _compress_batch_mixed(clips, tpf: int, base_scale: float, lanes, gather: boo
     for i, x in enumerate(clips):
         st = lanes[i % len(lanes)]
         with torch.cuda.stream(st):       # the plan's buffers are allocated (and owned) on the lane's stream
-            plan = _cached_plan(x.shape[0] // int(tpf), int(tpf), x.shape[1], x.dtype, dev, base_scale, "linear", 0,
+            plan = _cached_plan(x.shape[0] // tpfs[i], tpfs[i], x.shape[1], x.dtype, dev, base_scale, "linear", 0,
                                 False, gather, 0)
             plan.enqueue(x)
             taken.append(plan.take())
