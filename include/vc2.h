@@ -17,6 +17,10 @@
  *     "every op in the input dtype" behaviour: each torch op is evaluated exactly and rounded
  *     fp32 -> T (DESIGN.md "Numerics contract"); index outputs are int64 like torch's
  *   - row-major contiguous tensors; 16-byte aligned base pointers
+ *   - size limit: a row of D channels is read as D / 8 (16-bit) or D / 4 (fp32) 16-byte vectors, or as D
+ *     scalars when D is not a multiple of that; at most 1024 of them.  So D <= 8192 for 16-bit and <= 4096 for
+ *     fp32 when the row is whole vectors, D <= 1024 otherwise; a wider row gives VC2_ERR_UNSUPPORTED
+ *     (vc2_workspace_bytes already refuses it)
  */
 #ifndef VC2_H_
 #define VC2_H_
@@ -35,7 +39,7 @@ extern "C" {
 #define VC2_OK 0
 #define VC2_ERR_ARG (-1)          /* bad argument (null pointer, non-positive size, bad dtype) */
 #define VC2_ERR_SHAPE (-2)        /* rows not divisible by tokens-per-frame (torch .view RuntimeError) */
-#define VC2_ERR_UNSUPPORTED (-3)  /* shape outside what the kernels cover (see vc2_limits) */
+#define VC2_ERR_UNSUPPORTED (-3)  /* shape outside what the kernels cover (size limit above) */
 #define VC2_ERR_LAUNCH (-4)       /* hipLaunch failure; message in vc2_last_error() */
 #define VC2_ERR_WORKSPACE (-5)    /* workspace too small */
 

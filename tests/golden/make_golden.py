@@ -4,6 +4,7 @@
 Runs only in the build container (needs /root/reference, which never travels to the GPU box):
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --wide-scalar     # only wide_scalar_cases.json
 
 It imports token_compressor.vidcom2 from /root/reference, feeds it the bit-portable synthetic
 inputs of vidcom2_amd/synth.py (regenerated from a seed at test time; only their sha256 is stored)
@@ -15,6 +16,7 @@ Files written
   core_cases.json    full-pass goldens (channel order, scores digests + samples, budgets, kept indices)
   topk_kat.npz       torch.topk(largest=False) tie-breaking known-answer tests
   scales_kat.json    compute_scales / ks known-answer tests on hand-made frame scores
+  wide_scalar_cases.json  16-bit D > 4096 and VEC = 1 rows, as core_cases but with the channel order as a digest
   misc_kat.json      exp tables (sha256 over all 65536 bit patterns), index mappers, error paths
 """
 from __future__ import annotations
@@ -60,8 +62,8 @@ def ref_pass(x, tpf, base):
     return dict(var=var, chan_idx=cidx, v=v, f=f, s=s, scales=scales, ks=ks, global_idx=g)
 
 
-def core_cases():
-    shapes = [  # name, F, N, D, base, model, dtypes, dists, seeds
+def core_cases(shapes=None):
+    shapes = shapes or [  # name, F, N, D, base, model, dtypes, dists, seeds
         ("toy", 4, 49, 64, 0.25, "qwen2_5_vl", ("f32", "bf16", "f16"), ("drift", "iid"), (0, 1, 2)),
         ("odd", 3, 50, 72, 0.3, "qwen2_vl", ("f32", "bf16", "f16"), ("drift",), (0, 1)),
         ("cfg1", 8, 196, 1024, 0.25, "llava_ov", ("f32", "bf16", "f16"), ("drift", "iid"), (0, 1, 2)),
@@ -110,6 +112,27 @@ def core_cases():
                     out.append(rec)
                     print(name, dn, dist, seed, "K", rec["K"], "stable", rec["stable"], rec["oracle"], flush=True)
     return out
+
+
+WIDE_SCALAR_SHAPES = [
+    # 16-bit D > 4096 (Qwen2.5-VL-32B / -72B hidden sizes): LDS-round channel selection, no fused k_var_select
+    ("wide5120", 4, 49, 5120, 0.25, "qwen2_5_vl", ("bf16", "f16"), ("iid",), (0,)),
+    ("wide8192", 3, 64, 8192, 0.25, "qwen2_5_vl", ("bf16",), ("iid",), (0,)),
+    # rows that are not a whole number of vectors (VEC = 1, scalar channel loops)
+    ("scalar16", 3, 33, 1001, 0.25, "qwen2_5_vl", ("bf16", "f16"), ("drift",), (0,)),
+    ("scalar32", 3, 49, 1022, 0.25, "qwen2_5_vl", ("f32",), ("iid",), (0,)),
+]
+
+
+def wide_scalar_cases():
+    """core_cases' records for WIDE_SCALAR_SHAPES, the channel order (up to 4096 entries) kept as the sha256 of its
+    int64 tensor."""
+    cases = core_cases(WIDE_SCALAR_SHAPES)
+    for c in cases:
+        c["chan_sha256"] = sha(torch.tensor(c.pop("chan_idx"), dtype=torch.int64))
+    json.dump(dict(generator="tests/golden/make_golden.py", torch=torch.__version__, cases=cases),
+              open(os.path.join(HERE, "wide_scalar_cases.json"), "w"), separators=(",", ":"))
+    print("wide / scalar cases:", len(cases))
 
 
 def topk_kat():
@@ -225,8 +248,11 @@ def misc_kat():
     print("misc KATs written; errors:", errs)
 
 
-def main():
+def main(argv):
     O.build()
+    wide_scalar_cases()
+    if "--wide-scalar" in argv:
+        return
     cases = core_cases()
     json.dump(dict(generator="tests/golden/make_golden.py", torch=torch.__version__, cases=cases),
               open(os.path.join(HERE, "core_cases.json"), "w"), separators=(",", ":"))
@@ -238,4 +264,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

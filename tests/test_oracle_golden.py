@@ -68,6 +68,35 @@ def test_full_pass_vs_reference(c):
         assert len(a) == len(b) and len(a & b) / len(b) > 0.95
 
 
+WIDE_SCALAR = load_json("wide_scalar_cases.json")["cases"]
+
+
+@pytest.mark.parametrize("mode", ["torch", "exact"])
+@pytest.mark.parametrize("c", WIDE_SCALAR, ids=case_id)
+def test_wide_and_scalar_rows_vs_reference(c, mode):
+    """16-bit D > 4096 and rows that are not whole vectors (tests/golden/wide_scalar_cases.json): channel order,
+    budgets and kept indices equal the reference's; half-precision scores bit for bit, fp32 within 1e-5."""
+    O.set_mode(mode)
+    try:
+        x = make_input(c["F"], c["N"], c["D"], c["dtype"], c["seed"], c["dist"])
+        assert synth.sha256_tensor(x) == c["x_sha256"], "synthetic generator is not bit-portable"
+        o = O.compress_indices(x, c["N"], c["base"])
+        _, var = O.select_low_var_channel_idx(x)
+    finally:
+        O.set_mode("exact")
+    assert synth.sha256_tensor(var) == c["var_sha256"]
+    assert synth.sha256_tensor(o["chan_idx"]) == c["chan_sha256"]
+    assert o["ks"].tolist() == c["ks"]
+    if c["dtype"] == "f32":
+        assert np.allclose(o["v"][0, :16].float().tolist(), c["v_head"], rtol=0, atol=1e-5)
+        assert np.allclose(o["f"][0, :16].float().tolist(), c["f_head"], rtol=0, atol=1e-5)
+    elif mode == "torch" or c["oracle"]["v_mismatch"] == c["oracle"]["f_mismatch"] == 0:
+        assert synth.sha256_tensor(o["v"]) == c["v_sha256"] and synth.sha256_tensor(o["f"]) == c["f_sha256"]
+    if mode == "torch" or c["stable"]:
+        assert o["global_idx"].tolist() == c["global_idx"]
+        assert synth.sha256_tensor(x[o["global_idx"]]) == c["out_sha256"]
+
+
 def test_stable_fraction_documented():
     """All fp32 and all small/medium bf16 fixtures are index-exact; what is not is half precision at
     >= 5k tokens (fp16) / >= 20k tokens (bf16), where the reference's own fp32 accumulation order
