@@ -5,6 +5,7 @@ Runs only in the build container (needs /root/reference, which never travels to 
 
     python tests/golden/make_golden.py
     python tests/golden/make_golden.py --wide-scalar     # only wide_scalar_cases.json
+    python tests/golden/make_golden.py --grid            # only grid_cases.json
 
 It imports token_compressor.vidcom2 from /root/reference, feeds it the bit-portable synthetic
 inputs of vidcom2_amd/synth.py (regenerated from a seed at test time; only their sha256 is stored)
@@ -17,6 +18,7 @@ Files written
   topk_kat.npz       torch.topk(largest=False) tie-breaking known-answer tests
   scales_kat.json    compute_scales / ks known-answer tests on hand-made frame scores
   wide_scalar_cases.json  16-bit D > 4096 and VEC = 1 rows, as core_cases but with the channel order as a digest
+  grid_cases.json    LLaVA-Video's grid pass (vidcom2_compression(model="llava_vid")): budgets, mapped indices, rows
   misc_kat.json      exp tables (sha256 over all 65536 bit patterns), index mappers, error paths
 """
 from __future__ import annotations
@@ -135,6 +137,45 @@ def wide_scalar_cases():
     print("wide / scalar cases:", len(cases))
 
 
+GRID_SHAPES = [  # name, F, D, base, dtype, dist, seed -- h = 13 (N = 169), img_feat [F * 13 * 14, D] from seed + 100
+    ("vid_bf16", 16, 3584, 0.15, "bf16", "drift", 0),
+    ("vid_f16", 16, 3584, 0.15, "f16", "drift", 1),
+    ("vid_f32", 8, 1024, 0.15, "f32", "iid", 0),
+    ("oneframe", 1, 512, 0.25, "bf16", "iid", 2),
+    ("lowbase", 12, 256, 0.01, "bf16", "drift", 3),      # k = 1 or 2 per frame: mostly newline rows
+    ("highbase", 6, 256, 0.9, "f16", "drift", 4),        # scales clamp at 1: whole frames kept
+]
+
+
+def grid_cases():
+    """The reference's llava_vid pass end to end on synth inputs.  Per case: budgets, the mapped grid indices (the
+    sha256 of their int64 tensor), the sha256 of the rows it returns, and whether the oracle's kept set equals the
+    reference's in each mode."""
+    h = 13
+    out = []
+    for name, F, D, base, dn, dist, seed in GRID_SHAPES:
+        x = synth.make(F, h * h, D, DT[dn], seed, dist)
+        img = synth.make(F, h * (h + 1), D, DT[dn], seed + 100, "iid")
+        r = ref_pass(x, h * h, base)
+        loc = r["global_idx"] - torch.repeat_interleave(torch.arange(F) * h * h, torch.tensor(r["ks"]))
+        g = R._map_grid_vid(list(torch.split(loc, r["ks"])), h)
+        rows = R.vidcom2_compression(x, model="llava_vid", base_scale=base, img_feat=img)
+        assert torch.equal(rows, img[g])
+        oracle = {}
+        for mode in ("torch", "exact"):
+            O.set_mode(mode)
+            o = O.vidcom2_compression(x, model="llava_vid", base_scale=base, img_feat=img)
+            oracle[mode] = bool(o.shape == rows.shape and torch.equal(o, rows))
+        O.set_mode("exact")
+        out.append(dict(name=name, F=F, N=h * h, h=h, D=D, base=base, dtype=dn, dist=dist, seed=seed,
+                        img_seed=seed + 100, x_sha256=sha(x), img_sha256=sha(img), ks=r["ks"], K=int(g.numel()),
+                        idx_sha256=sha(g), out_sha256=sha(rows), oracle=oracle))
+        print(name, dn, "K", out[-1]["K"], "oracle", oracle, flush=True)
+    json.dump(dict(generator="tests/golden/make_golden.py --grid", torch=torch.__version__, cases=out),
+              open(os.path.join(HERE, "grid_cases.json"), "w"), separators=(",", ":"))
+    print("grid cases:", len(out))
+
+
 def topk_kat():
     """torch.topk(largest=False) on tie-heavy vectors: both libstdc++ regimes, NaN, all-equal rows."""
     rng = np.random.RandomState(1234)
@@ -250,6 +291,9 @@ def misc_kat():
 
 def main(argv):
     O.build()
+    if "--grid" in argv:
+        grid_cases()
+        return
     wide_scalar_cases()
     if "--wide-scalar" in argv:
         return
@@ -261,6 +305,7 @@ def main(argv):
     topk_kat()
     scales_kat()
     misc_kat()
+    grid_cases()
 
 
 if __name__ == "__main__":

@@ -97,6 +97,33 @@ def test_wide_and_scalar_rows_vs_reference(c, mode):
         assert synth.sha256_tensor(x[o["global_idx"]]) == c["out_sha256"]
 
 
+GRID = load_json("grid_cases.json")["cases"]
+
+
+@pytest.mark.parametrize("mode", ["torch", "exact"])
+@pytest.mark.parametrize("c", GRID, ids=lambda c: f"{c['name']}-{c['dtype']}")
+def test_grid_pass_vs_reference(c, mode):
+    """LLaVA-Video's grid pass (tests/golden/grid_cases.json): the oracle's budgets, kept tokens mapped onto the
+    h x (h + 1) newline grid and gathered img_feat rows equal the reference's vidcom2_compression(model="llava_vid")."""
+    h, F = c["h"], c["F"]
+    O.set_mode(mode)
+    try:
+        x = make_input(F, c["N"], c["D"], c["dtype"], c["seed"], c["dist"])
+        img = synth.make(F, h * (h + 1), c["D"], DT[c["dtype"]], c["img_seed"], "iid")
+        assert synth.sha256_tensor(x) == c["x_sha256"] and synth.sha256_tensor(img) == c["img_sha256"]
+        o = O.compress_indices(x, c["N"], c["base"])
+        rows = O.vidcom2_compression(x, model="llava_vid", base_scale=c["base"], img_feat=img)
+    finally:
+        O.set_mode("exact")
+    assert o["ks"].tolist() == c["ks"]
+    loc = o["global_idx"] - torch.repeat_interleave(torch.arange(F) * c["N"], o["ks"])
+    g = O.map_grid_vid(list(torch.split(loc, c["ks"])), h)
+    assert g.numel() == c["K"] == sum(c["ks"]) + F * h
+    assert c["oracle"][mode]
+    assert synth.sha256_tensor(g) == c["idx_sha256"]
+    assert synth.sha256_tensor(rows) == c["out_sha256"] and torch.equal(rows, img[g])
+
+
 def test_stable_fraction_documented():
     """All fp32 and all small/medium bf16 fixtures are index-exact; what is not is half precision at
     >= 5k tokens (fp16) / >= 20k tokens (bf16), where the reference's own fp32 accumulation order
