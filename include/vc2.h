@@ -279,6 +279,28 @@ int vc2_keep_positions_batched(const uint8_t* video_mask, int64_t B, int64_t S, 
 int vc2_repad_rows(const void* src, int64_t B, int64_t S, int64_t D, int dtype, const int64_t* keep, int64_t Sp, void* dst,
                    int32_t* status, void* stream);
 
+/* ---- backward of the gathers (vidcom2_amd/autograd.py) -----------------------------------------------------------
+ * Both reproduce torch's backward of x[idx] / x[:, idx] -- zeros_like(x).index_put_(idx, g, accumulate=True) -- bit for
+ * bit for unique indices: a kept element comes back as 0 + g in fp32 rounded to T (-0.0 -> +0.0, a bf16 NaN -> 0x7FC0),
+ * every other element is +0.0.  Every output element is written exactly once (no zero-fill pass).
+ *
+ * vc2_rows_grad: backward of vc2_gather_rows / vc2_gather_scatter (fresh destinations) / the gather of vc2_compress* /
+ * vc2_repad_rows.  For each of n_src tensors (HOST arrays, as vc2_gather_scatter):
+ *     gsrcs[t][idx ? idx[j] : j] = gdsts[t][dst_row0 + j]   for j < n,  every other row of gsrcs[t] = 0
+ * n = min(n_dev[0], n_max) when n_dev (device) is given, else n_max; gdsts[t] holds gdst_rows[t] >= dst_row0 + n_max rows,
+ * gsrcs[t] gsrc_rows[t].  Entries idx[j] < 0 are skipped (pad slots).  idx given: inv_ws = device scratch of inv_len >=
+ * max(gsrc_rows) int32 (the inverse map: one memset, one launch), then one streaming launch.  status (optional device
+ * word) |= 1 for a duplicate index (the row then holds ONE of its gradients: the caller must fall back to an
+ * accumulating scatter), |= 2 for an index >= max(gsrc_rows) (skipped).
+ *
+ * vc2_cols_grad: backward of vc2_gather_cols: gx T[R, D], gx[r, idx[c]] = g[r, c] for c < C, zero elsewhere; g T[R, C].
+ * D <= 8192 (the channel inverse map lives in LDS).  status (optional) |= 1 duplicate column, |= 2 column outside [0, D). */
+int vc2_rows_grad(const void* const* gdsts, const int64_t* gdst_rows, void* const* gsrcs, const int64_t* gsrc_rows,
+                  int n_src, int64_t D, int dtype, const int64_t* idx, const int64_t* n_dev, int64_t n_max,
+                  int64_t dst_row0, int32_t* inv_ws, int64_t inv_len, int32_t* status, void* stream);
+int vc2_cols_grad(const void* g, int64_t R, int64_t C, int64_t D, int dtype, const int64_t* idx, void* gx,
+                  int32_t* status, void* stream);
+
 /* ---- frame-sharded multi-GPU building blocks -------------------------
  * A rank holds frames [f0, f0+F_local) of a video with F_total frames.  Between the local sweeps the Python
  * layer all-gathers three small fp64 / fp32 arrays over RCCL.  Exchanges 1 and 2 carry CANONICAL partials -- per

@@ -49,6 +49,8 @@ _SIGNATURES = {
     "vc2_keep_positions_batched": [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64,
                                    _vp, _i64, _vp, _vp, _vp, _vp, _vp],
     "vc2_repad_rows": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp],
+    "vc2_rows_grad": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp],
+    "vc2_cols_grad": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
     "vc2_stat_block_frames": [],
     "vc2_chan_stats": [_vp, _i64, _i64, _i64, _i32, _i64, _i32, _vp, _sz, _vp, _vp],
     "vc2_chan_var_from_stats": [_vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp],

@@ -4196,6 +4196,173 @@ __global__ __launch_bounds__(kRepadNT) void k_repad_rows(const unsigned char* __
   }
 }
 
+// ---- backward of the row / column gathers (vidcom2_amd/autograd.py) ---------------------------------------------------
+// torch's backward of x[idx] is zeros_like(x).index_put_(idx, g, accumulate=True): every kept element comes back as
+// 0 + g, evaluated in fp32 and rounded to T by c10's conversion -- -0.0 becomes +0.0, a bf16 NaN becomes c10's 0x7FC0.
+// acc0_* reproduce exactly that on the bits.
+__device__ __forceinline__ uint32_t acc0_bf16x2(uint32_t w) {
+  uint32_t out = 0;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    uint32_t b = (w >> (16 * h)) & 0xFFFFu;
+    b = (b & 0x7FFFu) > 0x7F80u ? 0x7FC0u : (b == 0x8000u ? 0u : b);
+    out |= b << (16 * h);
+  }
+  return out;
+}
+__device__ __forceinline__ uint16_t acc0_f16(uint16_t b) {
+  const _Float16 h = __builtin_bit_cast(_Float16, b);
+  return __builtin_bit_cast(uint16_t, static_cast<_Float16>(0.0f + static_cast<float>(h)));
+}
+template <int DT> __device__ __forceinline__ uint32_t acc0_word(uint32_t w) {
+  if constexpr (DT == VC2_F32) return __float_as_uint(0.0f + __uint_as_float(w));
+  else if constexpr (DT == VC2_BF16) return acc0_bf16x2(w);
+  else return uint32_t(acc0_f16(uint16_t(w & 0xFFFFu))) | (uint32_t(acc0_f16(uint16_t(w >> 16))) << 16);
+}
+// d[de] = 0 + s[se] (s null: zero)
+template <int DT>
+__device__ __forceinline__ void acc0_store_scalar(const unsigned char* s, int64_t se, unsigned char* d, int64_t de) {
+  if constexpr (DT == VC2_F32) {
+    reinterpret_cast<float*>(d)[de] = s ? 0.0f + reinterpret_cast<const float*>(s)[se] : 0.0f;
+  } else {
+    const uint16_t b = s ? reinterpret_cast<const uint16_t*>(s)[se] : uint16_t(0);
+    reinterpret_cast<uint16_t*>(d)[de] = DT == VC2_BF16 ? uint16_t(acc0_bf16x2(b)) : acc0_f16(b);
+  }
+}
+
+// Launch 1: inv[r] = j for every kept row r = idx[j] (j < n), inv pre-set to -1 by a memset.  A second claim of one row
+// (duplicate) sets status bit 1, an index >= inv_len bit 2; negative entries (repad_rows' pad slots) are skipped.
+__global__ __launch_bounds__(256) void k_rows_grad_inv(const int64_t* __restrict__ idx, const int64_t* __restrict__ n_dev,
+                                                       int64_t n_max, int32_t* __restrict__ inv, int64_t inv_len,
+                                                       int32_t* __restrict__ status) {
+  const int64_t n = n_dev ? min(n_dev[0], n_max) : n_max;
+  int bits = 0;
+  for (int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; j < n; j += int64_t(gridDim.x) * blockDim.x) {
+    const int64_t r = idx[j];
+    if (r < 0) continue;
+    if (r >= inv_len) { bits |= 2; continue; }
+    if (atomicCAS(&inv[r], -1, int32_t(j)) != -1) bits |= 1;
+  }
+  if (bits && status) atomicOr(status, bits);
+}
+
+// Launch 2: every row r of every gradient tensor is written exactly once -- 0 + gdst[row0 + inv[r]] or zeros -- one wave
+// per row, 16 B per lane with non-temporal stores (the k_repad_rows layout: up to 8 vectors per lane loaded before any is
+// stored, four rows per workgroup); a row that is not whole aligned 16-byte vectors takes the scalar path.  inv == null:
+// the identity list (gather_scatter without idx), row r < n takes gdst row r.
+constexpr int kRgNT = 256;
+constexpr int kRgU = 8;
+struct RowsGradArgs {
+  const unsigned char* gdst[kGSMaxSrc];
+  unsigned char* gsrc[kGSMaxSrc];
+  int64_t gsrc_rows[kGSMaxSrc];
+  int64_t row_bytes, dst_row0, n_max;
+  const int64_t* n_dev;
+  const int32_t* inv;
+};
+template <int DT>
+__global__ __launch_bounds__(kRgNT) void k_rows_grad(RowsGradArgs a) {
+  const int t = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const int64_t rows = a.gsrc_rows[t];
+  const int64_t n = a.n_dev ? min(a.n_dev[0], a.n_max) : a.n_max;
+  const int64_t nwaves = int64_t(gridDim.x) * (kRgNT / 64);
+  const unsigned char* g = a.gdst[t];
+  unsigned char* out = a.gsrc[t];
+  const bool vec = (a.row_bytes & 15) == 0 && ((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  for (int64_t r = int64_t(blockIdx.x) * (kRgNT / 64) + (threadIdx.x >> 6); r < rows; r += nwaves) {
+    const int64_t j = a.inv ? int64_t(a.inv[r]) : (r < n ? r : -1);
+    const unsigned char* s = (j >= 0 && j < n) ? g + (a.dst_row0 + j) * a.row_bytes : nullptr;
+    unsigned char* d = out + r * a.row_bytes;
+    if (vec) {
+      const int64_t nv = a.row_bytes >> 4;
+      const uint4* sv = reinterpret_cast<const uint4*>(s);
+      uint4* dv = reinterpret_cast<uint4*>(d);
+      for (int64_t t0 = 0; t0 < nv; t0 += 64 * kRgU) {
+        uint4 v[kRgU];
+#pragma unroll
+        for (int u = 0; u < kRgU; ++u) {
+          const int64_t e = t0 + u * 64 + lane;
+          v[u] = (s && e < nv) ? sv[e] : make_uint4(0u, 0u, 0u, 0u);
+        }
+#pragma unroll
+        for (int u = 0; u < kRgU; ++u) {
+          const int64_t e = t0 + u * 64 + lane;
+          if (e < nv) {
+            uint32_t* dw = reinterpret_cast<uint32_t*>(dv + e);
+            __builtin_nontemporal_store(acc0_word<DT>(v[u].x), dw);
+            __builtin_nontemporal_store(acc0_word<DT>(v[u].y), dw + 1);
+            __builtin_nontemporal_store(acc0_word<DT>(v[u].z), dw + 2);
+            __builtin_nontemporal_store(acc0_word<DT>(v[u].w), dw + 3);
+          }
+        }
+      }
+    } else {
+      const int64_t ne = a.row_bytes / Tr<DT>::ES;
+      for (int64_t e = lane; e < ne; e += 64) acc0_store_scalar<DT>(s, e, d, e);
+    }
+  }
+}
+
+// Backward of x[:, idx] (vidcom2.py:43): gx[r, idx[c]] = 0 + g[r, c], zero in the other columns.  Each workgroup builds
+// the channel inverse map in LDS (a duplicate column sets status bit 1, a column >= D bit 2) and then owns whole rows of
+// gx: every element written once, coalesced; the reads gather from one row of g at a time.
+constexpr int kCgNT = 256;
+constexpr int kCgMaxD = 8192;
+template <int DT>
+__global__ __launch_bounds__(kCgNT) void k_cols_grad(const unsigned char* __restrict__ g, int64_t R, int C, int D,
+                                                     const int64_t* __restrict__ idx, unsigned char* __restrict__ gx,
+                                                     int32_t* __restrict__ status) {
+  __shared__ int inv[kCgMaxD];
+  __shared__ int bits;
+  if (threadIdx.x == 0) bits = 0;
+  for (int d = threadIdx.x; d < D; d += kCgNT) inv[d] = -1;
+  __syncthreads();
+  int mine = 0;
+  for (int c = threadIdx.x; c < C; c += kCgNT) {
+    const int64_t d = idx[c];
+    if (d < 0 || d >= D) { mine |= 2; continue; }
+    if (atomicCAS(&inv[d], -1, c) != -1) mine |= 1;
+  }
+  if (mine) atomicOr(&bits, mine);
+  __syncthreads();
+  if (blockIdx.x == 0 && threadIdx.x == 0 && bits && status) atomicOr(status, bits);
+  constexpr int ES = Tr<DT>::ES;
+  constexpr int V = 16 / ES;
+  const bool vec = (D % V) == 0 && (reinterpret_cast<uintptr_t>(gx) & 15) == 0;
+  for (int64_t r = blockIdx.x; r < R; r += gridDim.x) {
+    const unsigned char* gr = g + r * int64_t(C) * ES;
+    unsigned char* xr = gx + r * int64_t(D) * ES;
+    if (vec) {
+      for (int d0 = threadIdx.x * V; d0 < D; d0 += kCgNT * V) {
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          if constexpr (ES == 4) {
+            const int c = inv[d0 + q];
+            w[q] = c >= 0 ? acc0_word<DT>(reinterpret_cast<const uint32_t*>(gr)[c]) : 0u;
+          } else {
+            const int c0 = inv[d0 + 2 * q], c1 = inv[d0 + 2 * q + 1];
+            const uint32_t lo = c0 >= 0 ? reinterpret_cast<const uint16_t*>(gr)[c0] : 0u;
+            const uint32_t hi = c1 >= 0 ? reinterpret_cast<const uint16_t*>(gr)[c1] : 0u;
+            w[q] = acc0_word<DT>(lo | (hi << 16));
+          }
+        }
+        uint32_t* dw = reinterpret_cast<uint32_t*>(xr + int64_t(d0) * ES);
+        __builtin_nontemporal_store(w[0], dw);
+        __builtin_nontemporal_store(w[1], dw + 1);
+        __builtin_nontemporal_store(w[2], dw + 2);
+        __builtin_nontemporal_store(w[3], dw + 3);
+      }
+    } else {
+      for (int d = threadIdx.x; d < D; d += kCgNT) {
+        const int c = inv[d];
+        acc0_store_scalar<DT>(c >= 0 ? gr : nullptr, c, xr, d);
+      }
+    }
+  }
+}
+
 // ---- known-answer-test kernels -------------------------------------------------------
 template <int DT>
 __global__ void k_kat_exp(const void* __restrict__ in, int64_t n, void* __restrict__ out) {
@@ -5328,6 +5495,55 @@ int vc2_repad_rows(const void* src, int64_t B, int64_t S, int64_t D, int dtype, 
                      static_cast<const unsigned char*>(src), S, keep, rows, Sp, D * (dtype == VC2_F32 ? 4 : 2),
                      static_cast<unsigned char*>(dst), status);
   return check_launch("repad_rows");
+}
+
+int vc2_rows_grad(const void* const* gdsts, const int64_t* gdst_rows, void* const* gsrcs, const int64_t* gsrc_rows,
+                  int n_src, int64_t D, int dtype, const int64_t* idx, const int64_t* n_dev, int64_t n_max,
+                  int64_t dst_row0, int32_t* inv_ws, int64_t inv_len, int32_t* status, void* stream) {
+  if (!gdsts || !gdst_rows || !gsrcs || !gsrc_rows) return fail(VC2_ERR_ARG, "null pointer");
+  if (n_src < 1 || n_src > kGSMaxSrc) return fail(VC2_ERR_ARG, "n_src=%d outside [1, %d]", n_src, kGSMaxSrc);
+  if (dtype < 0 || dtype > 2 || D <= 0 || n_max < 0 || dst_row0 < 0) return fail(VC2_ERR_ARG, "bad rows_grad arguments");
+  if (n_max > INT32_MAX) return fail(VC2_ERR_UNSUPPORTED, "n=%lld rows (the inverse map holds int32)", (long long)n_max);
+  RowsGradArgs a{};
+  int64_t rows_max = 0;
+  for (int t = 0; t < n_src; ++t) {
+    if (!gdsts[t] || !gsrcs[t]) return fail(VC2_ERR_ARG, "null tensor %d", t);
+    if (gsrc_rows[t] < 0 || gdst_rows[t] < dst_row0 + n_max)
+      return fail(VC2_ERR_ARG, "tensor %d: %lld gradient rows for rows %lld + %lld", t, (long long)gdst_rows[t],
+                  (long long)dst_row0, (long long)n_max);
+    a.gdst[t] = static_cast<const unsigned char*>(gdsts[t]); a.gsrc[t] = static_cast<unsigned char*>(gsrcs[t]);
+    a.gsrc_rows[t] = gsrc_rows[t];
+    rows_max = std::max(rows_max, gsrc_rows[t]);
+  }
+  if (idx && (!inv_ws || inv_len < rows_max))
+    return fail(VC2_ERR_ARG, "the inverse map needs %lld int32 entries (got %lld)", (long long)rows_max, (long long)inv_len);
+  a.row_bytes = D * (dtype == VC2_F32 ? 4 : 2); a.dst_row0 = dst_row0; a.n_max = n_max; a.n_dev = n_dev;
+  a.inv = idx ? inv_ws : nullptr;
+  if (rows_max == 0) return VC2_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (idx) {
+    if (hipMemsetAsync(inv_ws, 0xFF, size_t(rows_max) * 4, st) != hipSuccess)
+      return fail(VC2_ERR_LAUNCH, "inverse-map memset failed");
+    if (n_max > 0)
+      hipLaunchKernelGGL(k_rows_grad_inv, dim3(unsigned(std::min<int64_t>(cdiv(n_max, 256), 1024))), dim3(256), 0, st,
+                         idx, n_dev, n_max, inv_ws, rows_max, status);
+  }
+  const unsigned grid = unsigned(std::min<int64_t>(cdiv(rows_max, kRgNT / 64), 4096));
+  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_rows_grad<DT>), dim3(grid, unsigned(n_src)), dim3(kRgNT), 0, st, a));
+  return check_launch("rows_grad");
+}
+
+int vc2_cols_grad(const void* g, int64_t R, int64_t C, int64_t D, int dtype, const int64_t* idx, void* gx,
+                  int32_t* status, void* stream) {
+  if (!g || !idx || !gx) return fail(VC2_ERR_ARG, "null pointer");
+  if (dtype < 0 || dtype > 2 || R < 0 || C <= 0 || D <= 0 || C > D) return fail(VC2_ERR_ARG, "bad cols_grad arguments");
+  if (D > kCgMaxD) return fail(VC2_ERR_UNSUPPORTED, "D=%lld > %d channels", (long long)D, kCgMaxD);
+  if (R == 0) return VC2_OK;
+  const unsigned grid = unsigned(std::min<int64_t>(R, 2048));
+  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_cols_grad<DT>), dim3(grid), dim3(kCgNT), 0, static_cast<hipStream_t>(stream),
+                                            static_cast<const unsigned char*>(g), R, int(C), int(D), idx,
+                                            static_cast<unsigned char*>(gx), status));
+  return check_launch("cols_grad");
 }
 
 int vc2_gather_rows(const void* src, int64_t src_rows, int64_t D, int dtype, const int64_t* idx,

@@ -25,6 +25,7 @@ from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
+from . import autograd as _ag
 from ._ffi import DTYPE_CODE, check, lib, on_device, ptr, require_device, stream_ptr
 
 _check_rc = check          # (gather_scatter has a keyword argument named `check`)
@@ -56,8 +57,13 @@ def gather_scatter(srcs: Sequence[torch.Tensor], idx: Optional[torch.Tensor] = N
     the caller passes one, and -- check=True -- by an IndexError after one small read-back, like
     the torch indexing this replaces (an unreported skip would leave an uninitialised row in a fresh destination).  The
     model hooks pass lists that keep_positions has just validated, so they skip the second read-back.
+    Autograd: with fresh destinations (no `dsts`, no `dst_pos`) every destination is differentiable with respect to its
+    source and dsts[0]'s tail rows with respect to `tail` (vidcom2_amd/autograd.py); check=True also makes the backward
+    check `idx` for duplicates (torch's accumulating scatter then), check=False vouches for a duplicate-free list.  The
+    in-place form (caller's `dsts`) is not differentiable.
     """
     srcs = list(srcs)
+    srcs_user, tail_user, fresh = list(srcs), tail, dsts is None
     if not 1 <= len(srcs) <= MAX_SOURCES:
         raise ValueError(f"gather_scatter takes 1..{MAX_SOURCES} tensors, got {len(srcs)}")
     x0 = srcs[0]
@@ -113,6 +119,9 @@ def gather_scatter(srcs: Sequence[torch.Tensor], idx: Optional[torch.Tensor] = N
     _check_rc(rc, "vc2_gather_scatter")
     if check and int(status.item()) & 2:
         raise IndexError("gather_scatter: a row index is out of range for its source or destination tensor")
+    if fresh and _ag.wants_grad(*srcs_user, tail_user):
+        dsts = _ag.attach_rows(dsts, srcs_user, idx, n, tail=tail_user, n_dev=n_dev, dst_row0=dst_row0,
+                               validate=check and idx is not None)
     return dsts
 
 
@@ -277,7 +286,10 @@ def repad_rows(src: torch.Tensor, keep: torch.Tensor, out: Optional[torch.Tensor
     """out[b, j] = src[b, keep[b, j]] for src [B, S, D] (fp32 / bf16 / fp16) and keep int64 [B, S'], a zero row where
     keep[b, j] < 0 (vc2_repad_rows).  An entry >= S is not read: its row is zeroed and reported -- in `status` (device
     int32[1], bit 1) and, check=True, by an IndexError after one small read-back.  The hooks pass the list
-    keep_positions_batched has just validated and skip that read-back."""
+    keep_positions_batched has just validated and skip that read-back.
+    Autograd: a fresh `out` is differentiable with respect to `src` (pad slots get no gradient; check=True also makes the
+    backward check the list for duplicates); a caller-provided `out` is not."""
+    src_user, fresh = src, out is None
     require_device(src, "src")
     if src.dtype not in DTYPE_CODE:
         raise TypeError(f"unsupported dtype {src.dtype} (fp32 / bf16 / fp16 only)")
@@ -303,6 +315,11 @@ def repad_rows(src: torch.Tensor, keep: torch.Tensor, out: Optional[torch.Tensor
     _check_rc(rc, "vc2_repad_rows")
     if check and int(status.item()) & 2:
         raise IndexError(f"repad_rows: a keep entry is out of range for {S} positions per row")
+    if fresh and _ag.wants_grad(src_user):
+        # one index list over the flattened batch: b * S + keep[b, j], -1 for pad slots (and entries the forward zeroed)
+        rows = torch.arange(B, dtype=torch.int64, device=src.device)[:, None] * S + keep
+        flat_idx = torch.where((keep >= 0) & (keep < S), rows, torch.full_like(rows, -1)).reshape(-1)
+        out = _ag.attach_rows([out], [src_user], flat_idx, B * Sp, validate=check, row_len=D)[0]
     return out
 
 

@@ -25,6 +25,7 @@ from __future__ import annotations
 
 import torch
 
+from ..autograd import attach_pool, wants_grad
 from ..vidcom2 import vidcom2_compression
 from ._intercept import original_method, retention_ratio, shadow
 
@@ -115,6 +116,9 @@ def _fused_pool(model, pool_inner, image_feature, args, kwargs):
         return None          # torch's other bilinear kernel (out_h + out_w > 128): another summation order
     from ..fused import pool_stats
     out, ws = pool_stats(image_feature, side, side, mode)
+    if wants_grad(image_feature):
+        # same forward bits (train and eval pick the same tokens); the backward is the model's own pooling Jacobian
+        out = attach_pool(out, image_feature, lambda xi: pool_inner(xi, *args, **kwargs))
     return out, ws
 
 
@@ -176,7 +180,8 @@ def cus_prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, atte
                     out = fused[0].as_subclass(_CompressOnFlatten)
                     out._vc2_stats_ws = fused[1]
                 if torch.is_tensor(newline_vec):
-                    out._vc2_newline = newline_vec.detach()
+                    # (kept attached when training: the fused tail then hands image_newline the gradient torch.cat gives it)
+                    out._vc2_newline = newline_vec if wants_grad(newline_vec) else newline_vec.detach()
                 return out
 
             patches["get_2dPool"] = get_2dPool

@@ -24,6 +24,7 @@ from typing import Any, Dict, List, Optional, Tuple
 import torch
 
 from . import _ffi
+from . import autograd as _ag
 from ._ffi import DTYPE_CODE, MAP_GRID_VID, MAP_LINEAR, MAP_LOCAL, check, lib, on_device, ptr, require_device, stream_ptr
 
 # vidcom2.py:7-13 -- 'mapper' selects the index mapping, 'tpf' the default tokens per frame
@@ -420,7 +421,10 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     """One whole pass: feature tensor resident in HBM -> kept rows + indices + budgets.
     tail ([m, D], e.g. LLaVA's newline embedding): written behind the kept rows by the gather launch itself;
     `rows` is then [K + m, D].  stats_ws: the workspace `fused.pool_stats` returned together with THIS tensor --
-    the pass then skips its first sweep."""
+    the pass then skips its first sweep.
+    Autograd: `rows` is differentiable (vidcom2_amd/autograd.py) with respect to the gathered-from tensor
+    (`flattened_feat`, or `img_feat` for grid_vid -- flattened_feat then gets none, as in the reference) and `tail`;
+    indices, budgets and scores are not."""
     x = _prep(flattened_feat, "flattened_feat")
     if x.dim() != 2:
         raise RuntimeError(f"flattened_feat must be 2-D [frames*tokens, dim], got {tuple(x.shape)}")
@@ -441,6 +445,7 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
             # the reference fails in img[_map_grid_vid(...)] (vidcom2.py:96) with an IndexError
             raise IndexError(f"index {need - 1} is out of bounds for dimension 0 with size {src.shape[0]}"
                              if src.dim() == 2 else "img_feat must be 2-D [rows, dim]")
+    tail_user = tail
     if tail is not None:
         tail = _prep(tail if tail.dim() == 2 else tail[None], "tail")
     if stats_ws is not None and (getattr(stats_ws, "_vc2_stats_for", None) != (R // tpf, tpf, D, x.dtype, x.data_ptr())
@@ -457,7 +462,11 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     plan.enqueue(x, src, tail, have_stats=stats_ws is not None, mirror=_EARLY_COUNT)
     if stats_ws is None and _PREALLOC and _PLAN_CACHE_MAX > 0 and plan.output_bytes() <= _SPARE_MAX_BYTES:
         plan.prepare_spare()              # (the GPU is busy for the next ~190 us: the next call's outputs cost nothing here)
-    return plan.finish()
+    res = plan.finish()
+    gsrc = img_feat if mapper == "grid_vid" else flattened_feat
+    if gather and _ag.wants_grad(gsrc, tail_user):
+        res.rows = _ag.attach_rows([res.rows], [gsrc], res.global_idx, res.K, tail=tail_user)[0]
+    return res
 
 
 _LANES: dict = {}
@@ -492,7 +501,22 @@ def compress_batch(clips, tpf: int, base_scale: float = 0.25, in_flight: int = B
     `tpf` may also be a sequence of one tokens-per-frame value per clip (videos of different grids).
     Storage: for clips of ONE shape every result is a VIEW into batch-wide buffers (one allocation per output kind), so
     keeping any clip's rows / indices alive keeps the whole batch's buffers alive (n * capacity * D elements);
-    own_storage=True hands every clip its own tensors instead (one extra device copy of the kept rows)."""
+    own_storage=True hands every clip its own tensors instead (one extra device copy of the kept rows).
+    Autograd: every clip's rows are differentiable with respect to that clip (vidcom2_amd/autograd.py)."""
+    clips = list(clips)
+    if _ag.wants_grad(*clips):
+        return [_attach_clip(r, c) for r, c in zip(_compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage),
+                                                   clips)]
+    return _compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage)
+
+
+def _attach_clip(res: CompressionResult, clip: torch.Tensor) -> CompressionResult:
+    if res.rows is not None and _ag.wants_grad(clip):
+        res.rows = _ag.attach_rows([res.rows], [clip], res.global_idx, res.K)[0]
+    return res
+
+
+def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool, own_storage: bool):
     clips = [_prep(c, "clip") for c in clips]
     if not clips:
         return []
@@ -631,7 +655,8 @@ def low_var_channel_order(x: torch.Tensor, ratio: float = 0.5) -> torch.Tensor:
 
 @_guarded
 def select_low_var_channels(x: torch.Tensor, ratio: float = 0.5) -> torch.Tensor:
-    """Reference: vidcom2.py:38-43.  Returns x[:, idx] -- a copy, columns in topk order."""
+    """Reference: vidcom2.py:38-43.  Returns x[:, idx] -- a copy, columns in topk order (differentiable w.r.t. x)."""
+    x_user = x
     x = _prep(x, "x")
     if x.dim() != 2:
         raise RuntimeError("select_low_var_channels expects a 2-D [tokens, dim] tensor")
@@ -642,6 +667,8 @@ def select_low_var_channels(x: torch.Tensor, ratio: float = 0.5) -> torch.Tensor
     if R and C:
         check(lib().vc2_gather_cols(ptr(x), R, D, DTYPE_CODE[x.dtype], ptr(idx), C, ptr(out), stream_ptr(x.device)),
               "vc2_gather_cols")
+    if C and _ag.wants_grad(x_user):
+        out = _ag.attach_cols(out, x_user, idx)
     return out
 
 
@@ -791,15 +818,19 @@ def _map_grid_vid(indices: List[torch.Tensor], h: int) -> torch.Tensor:
 
 @_guarded
 def _gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    src_user = src
     src = _prep(src, "features")
     K = idx.numel()
     out = torch.empty((K,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
     if K == 0:
-        return out
+        return _ag.attach_rows([out], [src_user], idx, 0)[0] if _ag.wants_grad(src_user) else out
     D = src[0].numel()
     kdev = torch.tensor([K, 0], dtype=torch.int64, device=src.device)
     check(lib().vc2_gather_rows(ptr(src), src.shape[0], D, DTYPE_CODE[src.dtype], ptr(idx), ptr(kdev), K, ptr(out),
                                 stream_ptr(src.device)), "vc2_gather_rows")
+    if _ag.wants_grad(src_user):
+        # (a caller's index list: the backward checks it for duplicates and then accumulates like torch)
+        out = _ag.attach_rows([out], [src_user], idx, K, validate=True)[0]
     return out
 
 
