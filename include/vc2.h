@@ -259,6 +259,8 @@ int vc2_keep_positions(const uint8_t* video_mask, int64_t S, const int64_t* kept
  *                            (attention_mask NULL: 1 in the kept slots)
  *   pos_out (optional, needs pos int64[R, B, S], R <= 4)  every plane gathered at keep_out; a pad slot holds the plane's
  *                            value at the row's first existing pad slot (attention_mask == 0), 0 when the row has none.
+ *                            Without text_row0 the values are only copied, never computed on: any 64-bit payload
+ *                            (e.g. the bits of fp64 positions, whose 0.0 is the all-zero word) comes back exactly.
  *                            text_row0: plane 0 holds text positions instead -- in a kept slot with attention_mask != 0
  *                            its rank among those slots of the row (0, 1, ...), in the other slots the pad value.
  * row_ws: device scratch of 4 * B int64.  counts_out (optional; device memory, or pinned host memory that is then stored

@@ -4,9 +4,13 @@
     from vidcom2_amd.models.qwen2_5_vl import Qwen2_5_VLModel_forward
     from vidcom2_amd.models.qwen2_vl import Qwen2VL_ViT_forward, Qwen2VLGeneration_forward
     from vidcom2_amd.models.qwen3_vl import Qwen3VLModel_forward
+    from vidcom2_amd.models.qwen2_5_omni import Qwen2_5OmniThinker_forward
+    from vidcom2_amd.models.qwen3_omni import Qwen3OmniMoeThinker_forward
 
 Same names, same installation (`types.MethodType(hook, model)`), same env knobs (`COMPRESSOR`,
 `R_RATIO`); implemented as wrappers around the installed model's own methods, see `_intercept.py`.
+The two Omni hooks (Qwen2.5-Omni, Qwen3-Omni) sit on the thinker's `forward`; their semantics are the Qwen2.5-VL /
+Qwen3-VL hooks applied to the thinker (the reference's Omni hooks are not in its checkout, see `qwen2_5_omni.py`).
 """
 from __future__ import annotations
 
@@ -25,6 +29,8 @@ def install(model, force: bool = False) -> bool:
     LLaVA-OneVision / LLaVA-Video : `model.prepare_inputs_labels_for_multimodal`
     Qwen2.5-VL / Qwen2-VL / Qwen3-VL : `forward` of the inner `*Model` (`model.model` of a
                                     `*ForConditionalGeneration`)
+    Qwen2.5-Omni / Qwen3-Omni      : `forward` of the thinker (`model.thinker` of the outer model, which also gets
+                                    the audio-output gate on its `generate`; or the bare thinker)
     """
     if not (force or compressor_enabled()):
         return False
@@ -32,6 +38,14 @@ def install(model, force: bool = False) -> bool:
     if hasattr(model, "prepare_inputs_labels_for_multimodal"):
         from .llava import cus_prepare_inputs_labels_for_multimodal as hook
         model.__dict__["prepare_inputs_labels_for_multimodal"] = types.MethodType(hook, model)
+        return True
+    omni = _omni_hook(names)
+    if omni is not None and hasattr(model, "thinker"):
+        from .qwen2_5_omni import install_outer
+        install_outer(model, omni)
+        return True
+    if omni is not None and any(n.endswith("ThinkerForConditionalGeneration") for n in names):
+        model.__dict__["forward"] = types.MethodType(omni, model)
         return True
     inner = model.model if any(n.endswith("ForConditionalGeneration") for n in names) else model
     inner_names = {k.__name__ for k in type(inner).__mro__}
@@ -45,3 +59,13 @@ def install(model, force: bool = False) -> bool:
         raise TypeError(f"vidcom2_amd.models.install: no hook for {type(model).__name__}")
     inner.__dict__["forward"] = types.MethodType(hook, inner)
     return True
+
+
+def _omni_hook(names):
+    if any(n.startswith("Qwen3OmniMoe") for n in names):
+        from .qwen3_omni import Qwen3OmniMoeThinker_forward
+        return Qwen3OmniMoeThinker_forward
+    if any(n.startswith("Qwen2_5Omni") for n in names):
+        from .qwen2_5_omni import Qwen2_5OmniThinker_forward
+        return Qwen2_5OmniThinker_forward
+    return None

@@ -299,12 +299,16 @@ class _LanguageModelShim:
         vpm = vpm.to(embeds.device).bool() if torch.is_tensor(vpm) else None
         deep = kwargs.get("deepstack_visual_embeds") if vpm is not None else None
         pos = kwargs.get("position_ids")
-        pos_in, text_row0, squeeze = None, False, False
+        pos_in, text_row0, squeeze, as_bits = None, False, False, False
         if torch.is_tensor(pos):
             pos_in = pos.to(embeds.device)
             if pos_in.dim() == 2:
                 pos_in, squeeze = pos_in[None], True
             text_row0 = pos_in.shape[0] == 4
+            if pos_in.is_floating_point() and not text_row0:
+                # Qwen3-Omni's TMRoPE positions are fp32 and may be fractional.  Without text_row0 the layout only copies
+                # position values (pad value 0 = the bits of 0.0), so they travel exactly as the 64-bit words of an fp64
+                pos_in, as_bits = pos_in.to(torch.float64).view(torch.int64), True
         elif pos is None and "position_ids" in kwargs:
             # the positions the batch-1 path builds for the row alone (text 0.., rope = position in the unpadded row)
             base = torch.where(am64 != 0, am64.cumsum(1) - 1, torch.zeros((), dtype=torch.int64, device=embeds.device))
@@ -331,7 +335,8 @@ class _LanguageModelShim:
         mask = lay.mask if am_dtype == torch.int64 else lay.mask.to(am_dtype)
         kwargs["attention_mask"] = mask if am is None else mask.to(am.device)
         if pos_in is not None:
-            out = lay.pos.to(pos.dtype) if torch.is_tensor(pos) else lay.pos
+            out = lay.pos.view(torch.float64) if as_bits else lay.pos
+            out = out.to(pos.dtype) if torch.is_tensor(pos) else out
             kwargs["position_ids"] = out[0] if squeeze else out
         cp = kwargs.get("cache_position")
         if torch.is_tensor(cp) and cp.dim() == 1 and cp.numel() == S:
