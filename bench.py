@@ -9,12 +9,15 @@
       per-frame budgets; cfg5: per clip) goes to DIR/<name>.npy as float32 / float64, 64 MB at most in all (larger rows
       arrays: a fixed seeded sample of rows, numbers in <name>_sample_rows.npy).  Inputs are seeded: the same arguments
       give the same inputs on every run, so two builds can be compared output for output.
+  --full: everything beyond the headline figure as well -- the CPU parity gate and CPU baselines before timing, and
+      after it the roofline / per-kernel leg, the other input states, the median, the exchange timings and the side
+      legs listed below.  Without it a run sets up, warms up, times the K steps, dumps and prints the line.
 
 A "step" = one whole pass over one batch of synthetic frame-token embeddings already resident in
 HBM: channel selection, scoring, budgets, per-frame selection and the kept-row gather
 (vidcom2.py:15-36).  Metric (BASELINE.json): input video tokens compressed per second at the
-stated retain ratio, with kept indices / budgets bit-exact vs the reference oracle (checked here on
-every run before timing).
+stated retain ratio, with kept indices / budgets bit-exact vs the reference oracle (checked by the
+test suite, and by a --full run before timing).
 
 N = 1 : workload "target" = 128 frames x 196 tokens x 3584-d bf16, 25 % retain (the shape
         BASELINE.json's north-star target is quoted on); cfg2 (32x196x3584) is reported beside it.
@@ -30,7 +33,8 @@ exits), VC2_BENCH_COLL_TIMEOUT=<s> (collective timeout, default 600), VC2_BENCH_
 the CPU-baseline sweep), VC2_BENCH_FORCE_DIST=1 (the sharded path and its collectives at world size 1),
 VC2_BENCH_ONE_GPU=1 + VC2_BENCH_BACKEND=gloo (tests: every rank on cuda:0).
 
-One JSON line on rank 0 (see the repo prompt for the contract), with extra objects:
+One JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), with extra objects (of a
+--full run; a plain run leaves "roofline" and "cpu_baseline" null and "pass_roofline" at the warm state):
   "roofline"      the dominant kernel's achieved algorithmic HBM rate (hipEvent-timed inside this run)
   "roofline_big"  the same for a > 256 MiB working set (cfg3), where the Infinity Cache cannot hold X
   "cpu_baseline"  the reference CPU path on this box's host cores: kind "port", flavour "torch-restatement" (the same
@@ -297,7 +301,7 @@ def bench_replicas(args, rank, world, dev, vc, _ffi, synth):
     clips = [synth.make(F, N, D, dtype, seed=rank * mine + i, dist="drift").to(dev) for i in range(min(mine, 4))]
     clips = [clips[i % len(clips)] for i in range(mine)]        # (>4 clips per rank: the same four again -- timing only)
     res0 = vc.vidcom2.compress_batch(clips[:1], N, base)[0]
-    if rank == 0 and not args.no_cpu_baseline:                  # parity gate on the first clip
+    if args.full and rank == 0 and not args.no_cpu_baseline:    # parity gate on the first clip
         import oracle
         oracle.set_mode("torch")
         ref = oracle.compress_indices(clips[0].cpu(), N, base)
@@ -345,8 +349,10 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="target", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity gate, CPU baselines, roofline and side measurements (off: the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the parity gate and CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed to DIR/<name>.npy (every rank: _rank<r> suffixes)")
     args = ap.parse_args()
@@ -417,7 +423,7 @@ def main():
         x32 = synth.make_fp32_frames(F_total, N, D, rank * F, F, seed=0, dist="drift")
         x = synth.to_torch(x32, dtype).reshape(F * N, D).to(dev)
         del x32
-        if force and world == 1:
+        if force and world == 1 and args.full:
             x_cpu = x.cpu()                            # (one rank: the CPU reference can check the sharded path too)
 
     if not dist_on:
@@ -430,11 +436,11 @@ def main():
         step = lambda: sc.enqueue(x)            # noqa: E731
         finish = sc.finish
 
-    # ---- parity gate: kept indices + budgets must equal the CPU reference path's before anything is timed ------
+    # ---- parity gate (--full): kept indices + budgets must equal the CPU reference path's before anything is timed ----
     cpu = None
     step()
     res = finish()
-    if x_cpu is not None and not args.no_cpu_baseline:
+    if args.full and x_cpu is not None and not args.no_cpu_baseline:
         cpu, ref = cpu_baselines(x_cpu, N, base, budget_s=10.0 if F_total * N <= 30000 else 3.0)
         ok = res.ks.cpu().tolist() == ref["ks"].tolist() and torch.equal(res.global_idx.cpu(), ref["global_idx"])
         if not ok:
@@ -442,8 +448,9 @@ def main():
     K = res.K
 
     # ---- timed region -------------------------------------------------------------------------------
-    # (setup, not warm-up: the CPU parity gate above kept the GPU idle for ~20 s and it comes back clocked down; a third
-    # of a second of passes brings the clocks up before the W warm-up steps and the K timed steps of the contract)
+    # (setup, not warm-up: the CPU parity gate above (--full) kept the GPU idle for ~20 s and it comes back clocked down,
+    # and a plain run's GPU sat idle while the host made the input; a third of a second of passes brings the clocks up
+    # before the W warm-up steps and the K timed steps of the contract)
     # (More than one rank: a FIXED number of passes.  A loop bounded by each rank's own clock ran 30 passes on one rank
     #  and 40 on the other every so often -- mismatched all-gathers, both ranks hung until the 30-minute collective
     #  timeout: the intermittent hang of the two-rank tests, found with VC2_BENCH_WATCHDOG in round 4.)
@@ -465,10 +472,6 @@ def main():
     ms = elapsed / args.steps * 1e3
     tokens_per_s = F_total * N / (elapsed / args.steps)
 
-    # ---- roofline leg: same steps again with hipEvents around every kernel --------------------------
-    kern = kernel_profile(step, args.steps, _ffi)
-    roof = roofline_of(kern, F, N, D, es, K, args.workload, world)
-
     out = {
         "metric": "video-tokens compressed/sec at 25% retain; kept-index bit-exact vs ref",
         "value": round(tokens_per_s, 1), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
@@ -479,20 +482,31 @@ def main():
                                f"retain {base}" + (f", frame-sharded {F} frames/GPU, 4 RCCL all-gathers" if dist_on else ""),
                    "frames_per_gpu": F,
                    "kept_tokens": K, "parallelism": f"frame-shard x{world}" if dist_on else "single GPU"},
-        "roofline": roof,
+        "roofline": None,
         "cpu_baseline": cpu,
         "pass_roofline": {"alg_bytes": alg_bytes_pass(F, N, D, es, base) * world,
                           "achieved_GBs": round(alg_bytes_pass(F, N, D, es, base) * world / (ms * 1e-3) / 1e9, 1),
                           "frac_of_8TBs_per_gpu": round(alg_bytes_pass(F, N, D, es, base) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)},
-        "kernels_us": kern,
-        "kernels_us_note": ("STAND-ALONE launches with hipEvents around each one (the ORDER replay and the norm fix-ups run as "
-                            "their own kernels here; in a real pass they ride in the sweep-2 / centre launches), so the sum "
-                            "exceeds ms_per_step; names vs rocprofv3: k_stats_reduce = k_var_from_stats, k_centres = "
-                            "k_frame_centres + k_video_centre, k_norm_colsum = k_norm_colsum2 (the streamlined sweep 2)"),
     }
-    extra_wanted = not dist_on and not args.no_extra
     out["mode"] = _ffi.get_mode() + (" (bit-exact to the CPU reference: boundary-fragile tokens replay torch's fp32 "
                                      "accumulation order)" if _ffi.get_mode() == "torch" else "")
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist_on:
+            torch.distributed.destroy_process_group()
+        return
+
+    # ---- roofline leg: same steps again with hipEvents around every kernel --------------------------
+    kern = kernel_profile(step, args.steps, _ffi)
+    out["roofline"] = roofline_of(kern, F, N, D, es, K, args.workload, world)
+    out["kernels_us"] = kern
+    out["kernels_us_note"] = ("STAND-ALONE launches with hipEvents around each one (the ORDER replay and the norm fix-ups "
+                              "run as their own kernels here; in a real pass they ride in the sweep-2 / centre launches), "
+                              "so the sum exceeds ms_per_step; names vs rocprofv3: k_stats_reduce = k_var_from_stats, "
+                              "k_centres = k_frame_centres + k_video_centre, k_norm_colsum = k_norm_colsum2 (the "
+                              "streamlined sweep 2)")
+    extra = not dist_on and not args.no_extra
     if not dist_on:
         # `value` / ms_per_step above is the WARM number: the loop re-reads one tensor, and X (171 MiB at the target
         # shape) is largely still in the 256 MiB Infinity Cache when the next step starts.  Two more states of the input,
@@ -530,7 +544,7 @@ def main():
         pr["producer_warm_frac_of_8TBs"] = round(ab / e_pw / 1e9 / HBM_PEAK_GBS, 4)
         pr["note"] = ("value / ms_per_step = the warm state; cold = three clips in turn; producer_warm = X written by a "
                       "device copy immediately before each pass (hipEvents around the pass)")
-        x_long = torch.cat([xs3[0], xs3[1], xs3[2], xs3[0]]) if (extra_wanted and args.workload == "target") else None
+        x_long = torch.cat([xs3[0], xs3[1], xs3[2], xs3[0]]) if (extra and args.workload == "target") else None
         del xs3, xw
     if not dist_on:
         out["median_ms_per_step"] = round(median_step_ms(step, max(args.steps, 20)), 4)
@@ -542,7 +556,6 @@ def main():
         out["exchanges_us"] = sc.exchange_times_us()
         sc.profile_exchanges(False)
 
-    extra = not dist_on and not args.no_extra
     # ---- side: the pass replayed from a hipGraph (serving loops capture it once) ------------------------
     if extra:
         try:

@@ -13,5 +13,5 @@ done
 python scripts/pmc_traffic.py $(find $out/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1) \
   $(find $out/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1) $tag > $out/pmc.txt 2>&1
 cp profiles/${tag}_pmc_traffic.json $out/ 2>/dev/null
-timeout -s KILL 900 python bench.py > $out/bench.json 2> $out/bench.err
+timeout -s KILL 900 python bench.py --full > $out/bench.json 2> $out/bench.err
 tail -c 3000 $out/bench.json

@@ -339,13 +339,27 @@ def test_bench_sharded_pass_on_rccl_at_world_one():
     """VC2_BENCH_FORCE_DIST=1: the frame-sharded pass with its four all-gathers on the `nccl` (= RCCL) backend, one
     rank -- all_gather_into_tensor on fp64 / fp32 device tensors really executes -- behind the CPU parity gate; the
     line reports the GPU count it ran on and the time of every exchange."""
-    out, d = _run_bench(["--gpus", "1", "--workload", "cfg2", "--steps", "3", "--warmup", "1", "--no-extra"],
+    out, d = _run_bench(["--gpus", "1", "--workload", "cfg2", "--steps", "3", "--warmup", "1", "--full", "--no-extra"],
                         {"VC2_BENCH_FORCE_DIST": "1", "MASTER_PORT": str(_free_port())})
     assert out.returncode == 0, out.stderr[-2000:]
     assert d is not None and d["n_gpus"] == 1 and d["config"]["parallelism"] == "frame-shard x1"
     assert d["cpu_baseline"] is not None                      # the parity gate ran (and passed) on the sharded result
     ex = d["exchanges_us"]
     assert set(ex) >= {"stats", "csum", "s"} and all(v["us"] > 0 and v["bytes_per_rank"] > 0 for v in ex.values())
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_only(tmp_path):
+    """Without --full a run times the steps, dumps the last step's outputs and prints the line: the contract's fields,
+    no parity gate, CPU baselines, per-kernel or side legs."""
+    out, d = _run_bench(["--gpus", "1", "--workload", "cfg2", "--steps", "3", "--warmup", "1",
+                         "--dump-outputs", str(tmp_path)])
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert d is not None and d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "tokens/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "bf16" and d["steps"] == 3 and d["warmup"] == 1
+    assert d["cpu_baseline"] is None and d["roofline"] is None
+    assert not {"kernels_us", "median_ms_per_step", "hipgraph_replay", "cfg3"} & set(d)
+    assert {p.name for p in tmp_path.iterdir()} == {"rows.npy", "global_idx.npy", "ks.npy"}
 
 
 @pytest.mark.gpu
@@ -384,6 +398,6 @@ def test_bench_cfg4_strong_scaling_two_ranks_on_one_gpu():
 @pytest.mark.gpu
 def test_bench_cfg5_replicas():
     """BASELINE configs[4]: 16 clips, replicas, no collective; parity gate on clip 0."""
-    out, d = _run_bench(["--gpus", "1", "--workload", "cfg5", "--steps", "1", "--warmup", "1"])
+    out, d = _run_bench(["--gpus", "1", "--workload", "cfg5", "--steps", "1", "--warmup", "1", "--full"])
     assert out.returncode == 0, out.stderr[-2000:]
     assert d["n_gpus"] == 1 and d["config"]["parallelism"] == "replicas x1" and d["dtype"] == "f16" and d["value"] > 0
