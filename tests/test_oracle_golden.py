@@ -124,6 +124,48 @@ def test_grid_pass_vs_reference(c, mode):
     assert synth.sha256_tensor(rows) == c["out_sha256"] and torch.equal(rows, img[g])
 
 
+LONG_FRAMES = load_json("long_frame_cases.json")["cases"]
+
+
+@pytest.mark.parametrize("c", LONG_FRAMES, ids=lambda c: f"{c['name']}-{c['F']}x{c['N']}x{c['D']}-{c['dtype']}-{c['dist']}")
+def test_long_frames_vs_reference(c):
+    """Frames of 256 to 8192 tokens (tests/golden/long_frame_cases.json): the oracle's 'torch' mode restates torch's
+    cascade there too -- a second level from 256 rows, a third from 4096, the tail columns' four chains of N / 4.
+    Channel order, budgets, kept indices and gathered rows equal the reference's; half-precision scores bit for bit,
+    fp32 within 1e-5."""
+    O.set_mode("torch")
+    try:
+        x = make_input(c["F"], c["N"], c["D"], c["dtype"], c["seed"], c["dist"])
+        assert synth.sha256_tensor(x) == c["x_sha256"], "synthetic generator is not bit-portable"
+        o = O.compress_indices(x, c["N"], c["base"])
+    finally:
+        O.set_mode("exact")
+    assert synth.sha256_tensor(o["chan_idx"]) == c["chan_sha256"]
+    assert o["ks"].tolist() == c["ks"]
+    g = o["global_idx"]
+    assert g.numel() == c["K"] and g[:8].tolist() == c["idx_head"] and g[-8:].tolist() == c["idx_tail"]
+    assert synth.sha256_tensor(g) == c["idx_sha256"] and synth.sha256_tensor(x[g]) == c["out_sha256"]
+    if c["dtype"] == "f32":
+        assert np.allclose(o["v"][0, :16].tolist(), c["v_head"], rtol=0, atol=1e-5)
+        assert np.allclose(o["f"][0, :16].tolist(), c["f_head"], rtol=0, atol=1e-5)
+    else:
+        assert synth.sha256_tensor(o["v"]) == c["v_sha256"] and synth.sha256_tensor(o["f"]) == c["f_sha256"]
+
+
+def test_long_frame_goldens_can_catch_a_missed_replay():
+    """The fixture's coverage: the N edges of the kernels' code paths, and fp16 `cancel` frames above 512 tokens --
+    simple and tail columns -- where fp64-exact centres differ from the reference's (a pass that skipped or misordered
+    a long-frame replay fails those)."""
+    assert {c["N"] for c in LONG_FRAMES} >= {256, 257, 512, 513, 576, 1020, 1021, 1024, 1296, 4095, 4096, 4097, 8188,
+                                             8189, 8192}
+    assert all(c["F"] * c["N"] * c["D"] <= 40 << 20 for c in LONG_FRAMES)
+    assert all(c["oracle_torch_mode"]["ks"] and c["oracle_torch_mode"]["idx"] for c in LONG_FRAMES)
+    cancel = [c for c in LONG_FRAMES if c["dtype"] == "f16" and c["dist"] == "cancel" and c["N"] > 512]
+    assert sum(c["centres_exact_ne"]["frame"] > 0 for c in cancel) >= 2
+    assert any(c["centres_exact_ne"]["frame_tail_columns"] > 0 for c in cancel)
+    assert {c["base"] for c in LONG_FRAMES} >= {0.0001, 0.005, 0.25, 1.0}
+
+
 def test_stable_fraction_documented():
     """All fp32 and all small/medium bf16 fixtures are index-exact; what is not is half precision at
     >= 5k tokens (fp16) / >= 20k tokens (bf16), where the reference's own fp32 accumulation order

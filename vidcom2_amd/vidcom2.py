@@ -398,6 +398,23 @@ def _khost_put(b: _KHost) -> None:
 _STATUS_FINAL = 1 << 62          # K_host[2] of vc2_compress_ex2: "this is the launch's final status word"
 
 
+_BUDGET_CAN_EXCEED: Dict[Tuple[int, Any], bool] = {}
+
+
+def _check_budgets(ks: torch.Tensor, N: int, dtype) -> None:
+    """The reference's budgets are round(RN_T(scale * N)) (vidcom2.py:72): with scale = 1.0 and an N that is not a T
+    value (bf16: N > 256 with more than 8 significant bits, e.g. 8188 -> 8192; fp16: N > 2048 with more than 11) a budget
+    exceeds the frame and torch.topk raises.  The kernels report the raw budget in `ks` and select min(k, N) tokens; the
+    device read that turns this into the reference's error is only made for such N (no budget can exceed any other N,
+    as scale <= 1)."""
+    key = (int(N), dtype)
+    can = _BUDGET_CAN_EXCEED.get(key)
+    if can is None:
+        can = _BUDGET_CAN_EXCEED[key] = float(torch.tensor(float(N)).to(dtype)) != float(N)
+    if can and int(ks.max()) > N:
+        raise RuntimeError("selected index k out of range")
+
+
 def _raise_status(status: int, cap: int, K: int) -> None:
     """K_out[1] of a pass (include/vc2.h): every bit is a 'cannot happen' condition the kernels check for instead of
     returning a silently wrong kept set."""
@@ -463,6 +480,7 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     if stats_ws is None and _PREALLOC and _PLAN_CACHE_MAX > 0 and plan.output_bytes() <= _SPARE_MAX_BYTES:
         plan.prepare_spare()              # (the GPU is busy for the next ~190 us: the next call's outputs cost nothing here)
     res = plan.finish()
+    _check_budgets(res.ks, tpf, x.dtype)
     gsrc = img_feat if mapper == "grid_vid" else flattened_feat
     if gather and _ag.wants_grad(gsrc, tail_user):
         res.rows = _ag.attach_rows([res.rows], [gsrc], res.global_idx, res.K, tail=tail_user)[0]
@@ -570,6 +588,8 @@ def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool,
     for i, (K, status) in enumerate(words):
         if status:
             _raise_status(int(status), p0.cap, int(K))
+    _check_budgets(ks_all, int(tpf), x0.dtype)
+    for i, (K, status) in enumerate(words):
         rows_i, idx_i, ks_i = (rows_all[i, :K] if gather else None), idx_all[i, :K], ks_all[i]
         if own_storage:
             rows_i, idx_i, ks_i = (rows_i.clone() if gather else None), idx_i.clone(), ks_i.clone()
@@ -597,7 +617,10 @@ def _compress_batch_mixed(clips, tpfs: List[int], base_scale: float, lanes, gath
                         t.record_stream(cur)
     for st in lanes[1:]:
         cur.wait_stream(st)                               # results are safe to use on the current stream
-    return CompressPlan.finish_many(taken)
+    res = CompressPlan.finish_many(taken)
+    for r, n, x in zip(res, tpfs, clips):
+        _check_budgets(r.ks, n, x.dtype)
+    return res
 
 
 @_guarded
