@@ -166,6 +166,88 @@ def test_long_frame_goldens_can_catch_a_missed_replay():
     assert {c["base"] for c in LONG_FRAMES} >= {0.0001, 0.005, 0.25, 1.0}
 
 
+RANGE = load_json("range_cases.json")
+
+
+def range_id(c):
+    return f"{c['name']}-{c['F']}x{c['N']}x{c['D']}"
+
+
+@pytest.mark.parametrize("c", RANGE["cases"], ids=range_id)
+def test_range_cases_vs_reference(c):
+    """Extreme feature magnitudes (tests/golden/range_cases.json, tests/_range_inputs.py): the oracle's 'torch' mode
+    equals the reference -- channel order, budgets, kept indices, rows; half-precision scores bit for bit, fp32 within
+    1e-5 -- on rows outside sweep 2's windows, below the clamp, with an fp32 sum of squares that overflows in torch (norm
+    inf), fp16 norms of inf, zero rows and non-finite elements.  The case meets its premise: the counts it targets,
+    worked out again on the host with the oracle's norms standing in for the reference's, are the golden's and non-zero."""
+    import _range_inputs as RI
+    x = RI.build(c)
+    assert synth.sha256_tensor(x) == c["x_sha256"], "input builder is not bit-portable"
+    O.set_mode("torch")
+    try:
+        o = O.compress_indices(x, c["N"], c["base"])
+        torch_norm = O.gaussian_debug(x, o["chan_idx"], c["N"])["norm"]
+    finally:
+        O.set_mode("exact")
+    exact_norm = O.gaussian_debug(x, o["chan_idx"], c["N"])["norm"]
+    assert synth.sha256_tensor(o["chan_idx"]) == c["chan_sha256"]
+    assert o["ks"].tolist() == c["ks"]
+    g = o["global_idx"]
+    assert g.numel() == c["K"] and g[:8].tolist() == c["idx_head"] and g[-8:].tolist() == c["idx_tail"]
+    assert synth.sha256_tensor(g) == c["idx_sha256"] and synth.sha256_tensor(x[g]) == c["out_sha256"]
+    if c["dtype"] == "f32":
+        assert np.allclose(o["v"][0, :16].tolist(), c["v_head"], rtol=0, atol=1e-5, equal_nan=True)
+        assert np.allclose(o["f"][0, :16].tolist(), c["f_head"], rtol=0, atol=1e-5, equal_nan=True)
+    else:
+        assert RI.score_sha256(o["v"]) == c["v_sha256"] and RI.score_sha256(o["f"]) == c["f_sha256"]
+    if c.get("grid_h"):                                   # LLaVA-Video's grid mapper and img_feat gather
+        img = RI.grid_img(c)
+        assert synth.sha256_tensor(img) == c["img_sha256"]
+        O.set_mode("torch")
+        try:
+            rows = O.vidcom2_compression(x, model="llava_vid", base_scale=c["base"], img_feat=img)
+        finally:
+            O.set_mode("exact")
+        assert rows.shape[0] == c["grid_K"] and synth.sha256_tensor(rows) == c["grid_out_sha256"]
+        assert c["oracle_grid"]["torch"]
+    assert RI.counts(x, o["chan_idx"], torch_norm, exact_norm) == c["counts"]
+    assert all(c["counts"][k] > 0 for k in c["premise"]), (c["premise"], c["counts"])
+
+
+def test_range_goldens_cover_the_windows():
+    """Every family, every sweep-2 form's shapes, and each limit: norms above and below both windows, below the clamp,
+    fp16 norms of inf and in (32768, 65504], fp16-subnormal rows, bf16 quotients below 2^-125, zero rows, rows inf or
+    NaN in more than half their channels (whose NaN variances are then selected) in every dtype, rows of D % 8 != 0
+    (VEC = 1), LLaVA-Video's grid pass; fp32 sums of squares that overflow (bf16 and fp32, whole clips and single rows) with the `exact` norm
+    differing from the reference's.  The scale sweeps list where the reference is invariant under 2^e, across both
+    bf16 window limits."""
+    cs = RANGE["cases"]
+    assert {c["family"] for c in cs} == set("ABCDE")
+    assert {(c["D"], c["dtype"]) for c in cs} >= {(3584, "bf16"), (3584, "f16"), (1024, "bf16"), (1024, "f16"),
+                                                  (4096, "f16"), (1536, "bf16"), (2048, "f16"), (1001, "bf16"),
+                                                  (1001, "f16"), (1024, "f32")}
+    assert any(c["D"] % 8 and c["counts"]["fp32_sumsq_overflow"] for c in cs)        # VEC = 1 rows (16-bit D % 8 != 0)
+    assert any(c.get("grid_h") == 13 and c["N"] == 169 for c in cs)                   # the llava_vid grid pass
+    corrupt = [c for c in cs if c["counts"]["nonfinite"]]                           # non-finite selected elements
+    assert {c["dtype"] for c in corrupt} == {"bf16", "f16", "f32"} and any(c["D"] == 3584 for c in corrupt)
+    assert any(c["N"] == 576 for c in cs) and any(c["N"] % 16 for c in cs)
+    tot = lambda k, **kw: sum(c["counts"][k] for c in cs if all(c[a] == b for a, b in kw.items()))   # noqa: E731
+    for k in ("bf16_norm_above", "bf16_norm_below", "below_clamp", "bf16_quot_below", "zero", "fp32_sumsq_overflow",
+              "exact_norm_ne"):
+        assert tot(k, dtype="bf16") > 0, k
+    for k in ("f16_norm_above", "f16_norm_over_max", "f16_norm_below", "f16_subnormal_rows", "zero"):
+        assert tot(k, dtype="f16") > 0, k
+    assert any(c["dtype"] == "f16" and c["counts"]["f16_norm_above"] > c["counts"]["f16_norm_over_max"] for c in cs)
+    assert tot("fp32_sumsq_overflow", dtype="f32") > 0 and tot("exact_norm_ne", dtype="f32") > 0
+    assert any(c["family"] == "B" and 0 < c["counts"]["fp32_sumsq_overflow"] < c["counts"]["rows"] for c in cs)
+    assert all(c["oracle_torch_mode"]["ks"] and c["oracle_torch_mode"]["idx"] for c in cs)
+    assert all(c["dtype"] == "f32" or c["oracle_torch_mode"]["scores"] for c in cs)
+    for s in RANGE["sweeps"]:
+        assert s["invariant_e"] == list(range(s["invariant_e"][0], s["invariant_e"][-1] + 1)), s["name"]
+        if s["dtype"] == "bf16":                         # norms 10..100 of the base clip: past 2^-39 and 2^40 both
+            assert s["invariant_e"][0] <= -43 and s["invariant_e"][-1] >= 40, s["name"]
+
+
 def test_stable_fraction_documented():
     """All fp32 and all small/medium bf16 fixtures are index-exact; what is not is half precision at
     >= 5k tokens (fp16) / >= 20k tokens (bf16), where the reference's own fp32 accumulation order

@@ -941,6 +941,12 @@ __device__ __forceinline__ void load_col_offsets(const int* __restrict__ cols, i
 // close to a T rounding boundary.  So: compute exactly (fp64), and only when the exact value is within
 // kFragileUlps fp32-ulps of a boundary replay torch's order for that token -- a few tokens per thousand.
 constexpr int kFragileUlpsNorm = 128;   // >= worst-case bound of the 8-chain FMA norm (232 * 2^-24 on the sum)
+// That margin presumes torch's fp32 sum of squares is finite.  From 2^-12 (relative) below FLT_MAX on -- far wider than the
+// chains' 232 * 2^-24 -- torch's sum may overflow: its norm is inf and x^ = +-0 (NaN for an inf element) where the exact
+// norm gives finite quotients.  Only sweep 2's exact path meets such rows (the fast paths' windows stay far below): in
+// 16-bit "torch order" mode they go to k_norm_fix's replay as well; fp32 rows, which have no replay, take the norm inf
+// where the exact sum rounds to inf in fp32.
+constexpr double kSumSqOverflow = 3.4028234663852886e38 * (1.0 - 1.0 / 4096.0);
 constexpr int kFragileUlpsDist = 48;    // >= worst-case bound of the cascade sum (~42 fp32 adds per lane)
 
 template <int DT> __device__ __forceinline__ bool near_T_boundary(float y, int margin) {
@@ -1311,14 +1317,15 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
     row_wait();
     if (n + kRowWaves < n1) row_issue<DT, VEC>(x, row + kRowWaves, D, CV, buf1, lane);
     // the norm rounded to T, the "torch order" queue, the denominator (F.normalize's clamp_min), den[row]
-    auto finish_norm = [&](float nrm32, int margin) -> float {
+    auto finish_norm = [&](float nrm32, int margin, bool ovf) -> float {
       const float norm = rnT<DT>(nrm32);
       // clamp_min(1e-12) is evaluated in fp32 then cast to T (fp16: 1e-12 -> 0 => 0/0 = NaN, as torch)
       float dn = rnT<DT>(fmaxf(norm, 1e-12f));
       if (norm != norm) dn = norm;
       // strict mode: where the norm sits within a few fp32 ulps of a T rounding boundary, torch's own fp32
-      // accumulation order decides the result -> queue the row (a few per thousand) for k_norm_fix
-      const bool flagged = strict && (strict == 2 || near_T_boundary<DT>(nrm32, margin));
+      // accumulation order decides the result -> queue the row (a few per thousand) for k_norm_fix; so does a sum
+      // of squares next to or past fp32 overflow (kSumSqOverflow)
+      const bool flagged = strict && (strict == 2 || ovf || near_T_boundary<DT>(nrm32, margin));
       if (flagged && lane == 0) {
         const int j = atomicAdd(tk + kTkFixCount, 1);
         if (j < nfix_cap) __hip_atomic_store(fixq + j, fixq_pack(row, dn), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1361,7 +1368,7 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
       const bool exact_div = __any(span.h.x > kBf16SpanLen || span.h.y > kBf16SpanLen) != 0;
       if (!exact_div) {
         const float nrm32 = float(sqrt(double(wave_sum_bcast_f32(ssq))));   // correctly rounded fp32 square root
-        const float dn = finish_norm(nrm32, kFragileUlpsNorm + acc_norm_ulps(NPLB));
+        const float dn = finish_norm(nrm32, kFragileUlpsNorm + acc_norm_ulps(NPLB), false);
         const float r = __builtin_amdgcn_rcpf(dn);
         if (lane == 0 && rflag) rflag[row] = 0;
 #pragma unroll
@@ -1380,6 +1387,7 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
     if (!done) {
       float nrm32;
       int margin = kFragileUlpsNorm;
+      bool ovf = false;
       if constexpr (ACC == 1 && DT != VC2_BF16) {
         float s0 = 0.f, s1 = 0.f;
 #pragma unroll
@@ -1396,9 +1404,15 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
           if constexpr (!kFastBf16) xv[i] = lds_elem<DT>(buf0, coff[i]);
           t = fma(double(xv[i]), double(xv[i]), t);
         }
-        nrm32 = float(sqrt(wave_sum_bcast(t)));
+        const double t2 = wave_sum_bcast(t);
+        nrm32 = float(sqrt(t2));
+        if constexpr (DT == VC2_F32) {
+          if (strict && float(t2) == INFINITY) nrm32 = INFINITY;   // (fp32, "torch order": strict is 1, see launch_norm_acc)
+        } else {
+          ovf = t2 >= kSumSqOverflow;
+        }
       }
-      const float dn = finish_norm(nrm32, margin);
+      const float dn = finish_norm(nrm32, margin, ovf);
       if (kFastBf16 && lane == 0 && rflag) rflag[row] = 1;
       const double inv = 1.0 / double(dn);
 #pragma unroll
@@ -1750,7 +1764,8 @@ __global__ __launch_bounds__(kRowWaves * 64, kS2Waves) void k_norm_colsum2(const
           t = fma(b, b, t);
           if (k + 1 < NP) asm volatile("" : "+v"(XA[k + 1]), "+v"(XB[k + 1]), "+v"(t));
         }
-        const float n32 = float(sqrt(wave_sum_bcast(t)));
+        const double t2 = wave_sum_bcast(t);
+        const float n32 = float(sqrt(t2));
         const float norm = rnT<DT>(n32);
         dn = rnT<DT>(fmaxf(norm, 1e-12f));
         if (norm != norm) dn = norm;
@@ -1764,7 +1779,7 @@ __global__ __launch_bounds__(kRowWaves * 64, kS2Waves) void k_norm_colsum2(const
           if constexpr (ORD != 0) chain[k] = pk_add_f32(chain[k], (f2_t){fa, fb});
           if (k + 1 < NP) asm volatile("" : "+v"(XA[k + 1]), "+v"(XB[k + 1]));
         }
-        meta = ((strict == 2 || near_T_boundary<DT>(n32, kFragileUlpsNorm)) ? 1u : 0u) | 2u;
+        meta = ((strict == 2 || t2 >= kSumSqOverflow || near_T_boundary<DT>(n32, kFragileUlpsNorm)) ? 1u : 0u) | 2u;
       }
       if (lane == (i & 63)) { pk_dn = dn; pk_meta = meta; }
       if ((i & 63) == 63) flush(i - 63, 64);
@@ -4710,9 +4725,10 @@ int launch_norm_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, c
   if (rider.perm) smem = std::max(smem, chan_order_lds(rider.D, rider.k, 4));      // the rider workgroup's arrays
   int rc = allow_big_lds(&k_norm_colsum<DT, VEC, NPLB, ACC, RIDER>, smem, "k_norm_colsum");
   if (rc) return rc;
+  // (fp32 has no replays -- cs.strict is 0 -- but "torch order" mode tells the sweep to overflow where torch does: 1)
   hipLaunchKernelGGL((k_norm_colsum<DT, VEC, NPLB, ACC, RIDER>), dim3(unsigned(p.S_W + (rider.perm ? (rider.parts & 0xFF) : 0))),
                      dim3(kRowWaves * 64), smem, st, x,
-                     int(p.N), int(p.D), p.CV, C, cols, cs.strict, p.S, p.S_q, p.R,
+                     int(p.N), int(p.D), p.CV, C, cols, p.dt == VC2_F32 ? (cur_mode() ? 1 : 0) : cs.strict, p.S, p.S_q, p.R,
                      wsp<float>(ws, p.o_den), wsp<double>(ws, p.o_part_col), wsp<int>(ws, p.o_ticket),
                      wsp<unsigned long long>(ws, p.o_nfixlist), int(p.R), wsp<uint8_t>(ws, p.o_rflag), rider);
   return VC2_OK;
