@@ -398,23 +398,48 @@ def test_compress_batch_matches_sequential():
 def test_compress_batch_same_shape_reuses_lanes_and_plans():
     """A batch of clips of one shape runs on compress_batch's kept lane streams with one cached plan per lane: a second
     call creates neither streams nor plans (the plan cache is keyed by stream -- fresh streams per call once meant fresh
-    plans and workspaces per call), and every clip still gets what it gets alone."""
+    plans and workspaces per call), and every clip still gets what it gets alone.  The same in a thread started through
+    `threading` and in one started through `_thread.start_new_thread` (which `threading.enumerate()` does not list),
+    while another thread comes and goes between the two calls: a thread's lanes live as long as the thread."""
+    import _thread
+    import threading
     from vidcom2_amd import vidcom2 as V
     xs = [make_input(16, 196, 1024, "f16", 70 + i, "drift").cuda() for i in range(7)]
     want = [V.compress(x, 196, 0.25) for x in xs]
-    V.compress_batch(xs, 196, 0.25)
     dev = xs[0].device
-    lanes_before = list(V._lane_streams(dev, V.BATCH_LANES - 1))
-    plans_before = dict(V._PLAN_CACHE)
-    got = V.compress_batch(xs, 196, 0.25)
-    assert [s.cuda_stream for s in V._lane_streams(dev, V.BATCH_LANES - 1)] == [s.cuda_stream for s in lanes_before]
-    assert set(V._PLAN_CACHE.keys()) == set(plans_before.keys())
-    assert all(V._PLAN_CACHE[k] is plans_before[k] for k in plans_before)
-    for g, w in zip(got, want):
-        assert g.K == w.K and torch.equal(g.global_idx, w.global_idx) and torch.equal(g.rows, w.rows) and torch.equal(g.ks, w.ks)
-    # the cached plans do not keep pointing into the batch's buffers
-    for p in V._PLAN_CACHE.values():
-        assert p.rows is None or p.rows.data_ptr() != got[0].rows.data_ptr()
+
+    def body():
+        V.compress_batch(xs, 196, 0.25)
+        lanes_before = list(V._lane_streams(dev, V.BATCH_LANES - 1))
+        plans_before = dict(V._PLAN_CACHE)
+        other = threading.Thread(target=V._lane_streams, args=(dev, 1))
+        other.start()
+        other.join()
+        got = V.compress_batch(xs, 196, 0.25)
+        assert [s.cuda_stream for s in V._lane_streams(dev, V.BATCH_LANES - 1)] == [s.cuda_stream for s in lanes_before]
+        assert set(V._PLAN_CACHE.keys()) == set(plans_before.keys())
+        assert all(V._PLAN_CACHE[k] is plans_before[k] for k in plans_before)
+        for g, w in zip(got, want):
+            assert g.K == w.K and torch.equal(g.global_idx, w.global_idx) and torch.equal(g.rows, w.rows) and torch.equal(g.ks, w.ks)
+        # the cached plans do not keep pointing into the batch's buffers
+        for p in V._PLAN_CACHE.values():
+            assert p.rows is None or p.rows.data_ptr() != got[0].rows.data_ptr()
+
+    body()
+    for start in (lambda fn: threading.Thread(target=fn).start(), lambda fn: _thread.start_new_thread(fn, ())):
+        done, errs = threading.Event(), []
+
+        def run():
+            try:
+                body()
+            except BaseException as e:  # noqa: BLE001
+                errs.append(e)
+            finally:
+                done.set()
+        start(run)
+        assert done.wait(300)
+        if errs:
+            raise errs[0]
 
 
 def test_selection_engine_loop_bounds_never_expire():
@@ -727,40 +752,64 @@ def test_early_count_mirror_and_spare_outputs_change_nothing():
         V.clear_plan_cache()
 
 
+class _HiddenFinal:
+    """Stands in for vidcom2._mirror_words (the host's one read of a pass's pinned status words): its next `n` reads
+    report the early status as `early` and the final status word as not arrived yet -- the late path of the host mirror,
+    forced instead of hoped for.  Reads after those see the real words."""
+
+    def __init__(self, real):
+        self.real, self.n, self.early = real, 0, 0
+
+    def hide(self, n, early=0):
+        self.n, self.early = n, early
+
+    def __call__(self, block):
+        if self.n > 0:
+            self.n -= 1
+            return self.early, None
+        return self.real(block)
+
+
 @pytest.mark.gpu
-def test_a_guard_hit_of_any_frame_reaches_the_caller():
+def test_a_guard_hit_of_any_frame_reaches_the_caller(monkeypatch):
     """Status bit 4 (a loop bound of the selection replay expired) raised from the workgroup of a NON-last frame -- the
-    last frame's workgroup writes the count and the early status words before the other selections end.  With the host
-    mirror armed the hit arrives in the mirror's FINAL word (K_host[2]): taken by finish() if it is already there, else
-    raised when the plan's next pass is enqueued (_settle).  Without the mirror the blocking copy sees it.  The stage
-    call (vc2_select: no pass-wide status word) reports it in K_out[1] as well."""
+    last frame's workgroup writes the count and the early status words before the other selections end.  Without the
+    host mirror the blocking copy sees it.  With the mirror armed the hit arrives in the mirror's FINAL word (K_host[2]):
+    taken by finish() if it is there already; if not, raised -- once -- when the plan's next pass is enqueued (_settle);
+    if the EARLY words carry it, finish() raises it -- once: the plan's next pass runs normally.  The stage call
+    (vc2_select: no pass-wide status word) reports it in K_out[1] as well."""
     import vidcom2_amd as vc
     from vidcom2_amd import vidcom2 as V
     dev = torch.device("cuda:0")
     F, N, D = 16, 196, 1024
     x = synth.make(F, N, D, torch.bfloat16, 3, "drift").to(dev)
     L = _ffi.lib()
+    words = _HiddenFinal(V._mirror_words)
+    monkeypatch.setattr(V, "_mirror_words", words)
     try:
-        for mirror in (False, True):
+        for how in ("blocking", "final_there", "late", "early") * 2:
+            mirror = how != "blocking"
             plan = V.CompressPlan(F, N, D, torch.bfloat16, dev, 0.25)
             plan.enqueue(x, mirror=mirror); good = plan.finish(); plan._settle()
             L.vc2_selftest_force_guard(3)                      # frame 3 of 16: not the workgroup that writes the count
             plan.new_outputs(); plan.enqueue(x, mirror=mirror)
-            raised = False
-            try:
-                plan.finish()
-            except RuntimeError as e:
-                raised = "selection replay" in str(e)
-            if not raised:                                     # the early words were clean: the final word must not be
-                assert mirror
+            if how == "final_there":
                 torch.cuda.synchronize()
+            words.hide({"late": 2, "early": 1}.get(how, 0), early=4 if how == "early" else 0)
+            if how == "late":
+                plan.finish()                                  # the early words are clean: the final word must not be
+                assert plan._late is not None
+                L.vc2_selftest_force_guard(-1)
                 with pytest.raises(RuntimeError, match="PREVIOUS pass.*selection replay"):
                     plan.new_outputs(); plan.enqueue(x, mirror=mirror)
+            else:
+                with pytest.raises(RuntimeError, match="selection replay"):
+                    plan.finish()
+                assert plan._late is None
             L.vc2_selftest_force_guard(-1)
-            torch.cuda.synchronize()
-            plan._late = None
             plan.new_outputs(); plan.enqueue(x, mirror=mirror); again = plan.finish(); plan._settle()
-            assert again.K == good.K and torch.equal(again.global_idx, good.global_idx)
+            assert again.K == good.K and torch.equal(again.global_idx, good.global_idx), how
+            assert words.n == 0, how
         # the stage call: K_out[1] carries the bit whichever workgroup stored the count
         scores = torch.rand(F, N, device=dev).to(torch.bfloat16)
         scales = torch.full((F,), 0.25, device=dev).to(torch.bfloat16)
@@ -814,42 +863,76 @@ def test_selection_engines_and_launch_forms_agree(shape):
 
 
 @pytest.mark.gpu
-def test_a_late_guard_hit_is_reported_when_the_plan_is_dropped():
-    """VERDICT r5 item 7 / ADVICE r5: a pass that returned on the early words of the host mirror and whose plan is never
-    used again -- dropped, cleared out of (or evicted from) the plan cache, or followed by an un-mirrored enqueue -- still
-    gets its final status word read: a RuntimeWarning where nothing may raise, the exception in front of ANY next pass."""
+def test_a_late_guard_hit_is_reported_when_the_plan_is_dropped(monkeypatch):
+    """VERDICT r5 item 7 / ADVICE r5-r6: a pass that returned on the early words of the host mirror and whose plan is
+    never used again -- dropped, cleared out of the plan cache, evicted from it by another thread, or followed by an
+    un-mirrored enqueue -- still gets its final status word read, exactly once: a RuntimeWarning where nothing may raise,
+    the exception in front of ANY next pass.  Every try is late by construction (_HiddenFinal: finish() and the settling
+    read see no final word; the settle then waits on the stream the pass was enqueued on and reads it again)."""
     import gc
+    import threading
     import warnings as W
     from vidcom2_amd import vidcom2 as V
     dev = torch.device("cuda:0")
     F, N, D = 16, 196, 1024
     x = synth.make(F, N, D, torch.bfloat16, 3, "drift").to(dev)
     L = _ffi.lib()
+    words = _HiddenFinal(V._mirror_words)
+    monkeypatch.setattr(V, "_mirror_words", words)
+    synced = []
+    real_sync = torch.cuda.Stream.synchronize
+    monkeypatch.setattr(torch.cuda.Stream, "synchronize", lambda st: (synced.append(st.cuda_stream), real_sync(st))[1])
 
-    def late_pass():
-        """a plan whose last pass returned early with a guard hit still on its way (None: finish() already saw it)"""
-        plan = V.CompressPlan(F, N, D, torch.bfloat16, dev, 0.25)
-        plan.enqueue(x, mirror=True); plan.finish(); plan._settle()
+    def reports(rec):
+        return sum("selection replay" in str(r.message) for r in rec)
+
+    def late(fn):
+        """fn() enqueues a pass with a guard hit on its way and returns on the pass's early words"""
         L.vc2_selftest_force_guard(3)
-        plan.new_outputs(); plan.enqueue(x, mirror=True)
+        words.hide(2)
         try:
-            plan.finish()
-        except RuntimeError:
-            plan = None
-        L.vc2_selftest_force_guard(-1)
-        torch.cuda.synchronize()
-        return plan
+            return fn()
+        finally:
+            L.vc2_selftest_force_guard(-1)
     try:
-        seen = 0
-        for how in ("del", "quiet", "plain_enqueue") * 4:
-            plan = late_pass()
-            if plan is None or plan._late is None:
+        for how in ("del", "quiet", "plain_enqueue", "evicted") * 3:
+            if how == "evicted":
+                # a cached plan with a pending hit, its pass on a stream of its own; ANOTHER thread evicts it and reports
+                # the hit (once), after waiting for THAT stream, not its own current one
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                V.clear_plan_cache()
+                with torch.cuda.stream(s):
+                    late(lambda: vc.compress(x, N, 0.25))
+                (plan,) = V._PLAN_CACHE.values()
+                assert plan._late is not None
+                rec, synced[:] = [], []
+
+                def evict():
+                    with W.catch_warnings(record=True) as r:
+                        W.simplefilter("always")
+                        vc.compress(x, N, 0.25)                  # (another thread: another key -- the oldest goes)
+                    rec.extend(r)
+                old_max, V._PLAN_CACHE_MAX = V._PLAN_CACHE_MAX, 1
+                try:
+                    th = threading.Thread(target=evict)
+                    th.start()
+                    th.join()
+                finally:
+                    V._PLAN_CACHE_MAX = old_max
+                assert plan not in V._PLAN_CACHE.values() and plan._late is None
+                assert reports(rec) == 1 and synced == [s.cuda_stream], (rec, synced)
+                plan._settle()                                   # (the owner: nothing left to report)
+                del plan
                 continue
-            seen += 1
+            plan = V.CompressPlan(F, N, D, torch.bfloat16, dev, 0.25)
+            late(lambda: (plan.enqueue(x, mirror=True), plan.finish()))
+            assert plan._late is not None, how                # every try takes the late path
             if how == "plain_enqueue":                           # an un-mirrored next pass settles the previous one too
                 with pytest.raises(RuntimeError, match="PREVIOUS pass.*selection replay"):
-                    plan.new_outputs(); plan.enqueue(x, mirror=False)
-                plan._late = None
+                    plan.enqueue(x, mirror=False)
+                plan.enqueue(x, mirror=False); plan.finish()     # ... once
+                del plan
                 continue
             with W.catch_warnings(record=True) as rec:
                 W.simplefilter("always")
@@ -857,24 +940,18 @@ def test_a_late_guard_hit_is_reported_when_the_plan_is_dropped():
                     del plan; gc.collect()
                 else:
                     plan.settle_quietly()
-            assert any("selection replay" in str(r.message) for r in rec), how
-        # (the early words normally precede the final one: at least one of the twelve tries must have been late)
-        assert seen >= 1
+                    plan.settle_quietly()
+                    del plan
+            assert reports(rec) == 1, how
         # the plan cache: clearing it settles its plans
-        V.clear_plan_cache()
         good = vc.compress(x, N, 0.25)
-        L.vc2_selftest_force_guard(3)
-        try:
-            vc.compress(x, N, 0.25)
-            late = True
-        except RuntimeError:
-            late = False
-        L.vc2_selftest_force_guard(-1)
-        torch.cuda.synchronize()
+        V.clear_plan_cache()
+        late(lambda: vc.compress(x, N, 0.25))
         with W.catch_warnings(record=True) as rec:
             W.simplefilter("always")
             V.clear_plan_cache()
-        assert (not late) or any("selection replay" in str(r.message) for r in rec)
+            V.clear_plan_cache()
+        assert reports(rec) == 1
         assert torch.equal(vc.compress(x, N, 0.25).global_idx, good.global_idx)
     finally:
         L.vc2_selftest_force_guard(-1)

@@ -19,7 +19,7 @@ import threading
 import time
 import warnings
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -98,6 +98,34 @@ def cascade_modelled(n: int) -> bool:
     return lp <= 6 and (((int(n) >> lp) + (1 << lp) - 1) >> lp) <= 8192
 
 
+class OutputSet(NamedTuple):
+    """The output tensors one pass writes (a plan's own, a fresh set per one-shot call, or one clip's slice of
+    compress_batch's batch-wide buffers): kept indices, budgets, kept rows (+ tail rows), scores, (K, status) words."""
+    idx: torch.Tensor                   # int64 [cap]
+    ks: torch.Tensor                    # int64 [F]
+    rows: Optional[torch.Tensor]        # T [cap + tail_rows, D] (None: no gather)
+    v: Optional[torch.Tensor]           # T [F, N] (None: no scores)
+    f: Optional[torch.Tensor]
+    kout: torch.Tensor                  # int64 [2]: (K, status), both written by every pass
+
+    def result(self, K, status) -> CompressionResult:
+        """The pass's result once its (K, status) words are on the host: raises on a nonzero status."""
+        K, cap = int(K), self.idx.shape[-1]
+        if status:
+            _raise_status(int(status), cap, K)
+        rows = None if self.rows is None else self.rows[:K + self.rows.shape[0] - cap]     # (+ the tail rows)
+        return CompressionResult(rows, self.idx[:K], self.ks, K, self.v, self.f)
+
+
+class _LateStatus(NamedTuple):
+    """A pass that finish() returned on the early words of its pinned mirror block: its final status word is still to be
+    read (CompressPlan._settle)."""
+    block: "_KHost"
+    cap: int
+    K: int
+    stream: "torch.cuda.Stream"         # the stream the pass was enqueued on
+
+
 class CompressPlan:
     """Pre-allocated buffers for repeated passes over one (F, N, D, dtype) shape.
 
@@ -129,34 +157,43 @@ class CompressPlan:
                           "keep their exactly rounded mean and may differ from the CPU reference by one ulp",
                           RuntimeWarning, stacklevel=3)
         self.ws = ws if ws is not None else _ffi.workspace(self.F, self.N, self.D, dtype, self.device)
-        self.kout = torch.empty(2, dtype=torch.int64, device=self.device)    # both words written by every pass
         # tail_rows: extra rows (LLaVA's newline embedding) the gather launch appends behind the kept ones
         self.tail_rows = int(tail_rows) if gather else 0
         self._gather, self._want_scores = bool(gather), bool(want_scores)
+        self.out = self._alloc_outputs()                 # the plan's own output set (enqueue without `out`, finish)
         self._spare = None
         # (K, status) mirrored by the selection launch into pinned host memory (vc2_compress_ex2): finish(early=True) gets
         # the count from there -- ~15 us before the pass ends, no device-to-host copy -- and returns while the gather runs
         self._khost = None
-        self._khost_armed = False
-        self._late = None                                # a pass that returned on its early status words (see _settle)
-        self.new_outputs()
+        self._armed = None                               # the stream of a mirrored pass that finish() has not seen yet
+        self._late = None                                # _LateStatus: read and cleared by _settle alone
+        self._settle_lock = threading.Lock()
 
-    def _alloc_outputs(self):
-        dt, dev = self.dtype, self.device
-        return (torch.empty(self.cap, dtype=torch.int64, device=dev),
-                torch.empty(self.F, dtype=torch.int64, device=dev),
-                torch.empty((self.cap + self.tail_rows, self.D), dtype=dt, device=dev) if self._gather else None,
-                torch.empty((self.F, self.N), dtype=dt, device=dev) if self._want_scores else None,
-                torch.empty((self.F, self.N), dtype=dt, device=dev) if self._want_scores else None,
-                torch.empty(2, dtype=torch.int64, device=dev))    # (K, status): both words written by every pass
+    # the plan's own outputs, read-only: a caller that wants the pass written elsewhere passes `enqueue(..., out=)`
+    idx = property(lambda self: self.out.idx)
+    ks = property(lambda self: self.out.ks)
+    rows = property(lambda self: self.out.rows)
+    v = property(lambda self: self.out.v)
+    f = property(lambda self: self.out.f)
+    kout = property(lambda self: self.out.kout)
+
+    def _alloc_outputs(self, n: Optional[int] = None) -> OutputSet:
+        """A fresh output set; with n: n sets in ONE allocation per output kind ([n, ...] tensors: compress_batch)."""
+        dt, dev, lead = self.dtype, self.device, () if n is None else (n,)     # (sizes as arguments: ~1 us less each)
+        return OutputSet(torch.empty(*lead, self.cap, dtype=torch.int64, device=dev),
+                         torch.empty(*lead, self.F, dtype=torch.int64, device=dev),
+                         torch.empty(*lead, self.cap + self.tail_rows, self.D, dtype=dt, device=dev) if self._gather else None,
+                         torch.empty(*lead, self.F, self.N, dtype=dt, device=dev) if self._want_scores else None,
+                         torch.empty(*lead, self.F, self.N, dtype=dt, device=dev) if self._want_scores else None,
+                         torch.empty(*lead, 2, dtype=torch.int64, device=dev))
 
     def new_outputs(self) -> None:
-        """Fresh output tensors (kept rows, indices, budgets, scores) for the next pass.  A plan that is re-used for
-        independent calls (the one-shot API's plan cache) calls this before every enqueue, so that a result handed out
+        """A fresh own output set (kept rows, indices, budgets, scores) for the next pass.  A plan that is re-used for
+        independent calls (the one-shot API's plan cache) takes one before every enqueue, so that a result handed out
         earlier is never overwritten -- the reference returns fresh tensors as well; workspace and status words stay.
         (`prepare_spare` may have made the set already, while the previous pass was running.)"""
         spare, self._spare = self._spare, None
-        self.idx, self.ks, self.rows, self.v, self.f, self.kout = spare if spare is not None else self._alloc_outputs()
+        self.out = spare if spare is not None else self._alloc_outputs()
 
     def output_bytes(self) -> int:
         """Bytes of ONE output set (kept rows, indices, budgets, scores, status words)."""
@@ -181,11 +218,13 @@ class CompressPlan:
 
     def enqueue(self, flat: torch.Tensor, gather_src: Optional[torch.Tensor] = None,
                 tail: Optional[torch.Tensor] = None, have_stats: bool = False, mirror: bool = False,
-                stream: Optional["torch.cuda.Stream"] = None) -> None:
+                stream: Optional["torch.cuda.Stream"] = None, out: Optional[OutputSet] = None) -> None:
         """have_stats: `self.ws` already holds flat's sweep-1 partials (fused.pool_stats wrote them on this
         stream), so the pass starts at the variance reduction.  mirror: the count is also written to pinned host
-        memory (finish(early=True))."""
+        memory (finish(early=True)).  out: the output set to write (one this plan's `_alloc_outputs` could have made;
+        the caller reads it) instead of the plan's own."""
         src = flat if gather_src is None else gather_src
+        o = self.out if out is None else out
         if have_stats:
             tag = getattr(self.ws, "_vc2_stats_for", None)
             if tag is not None and tag != (self.F, self.N, self.D, self.dtype, flat.data_ptr()):
@@ -199,26 +238,26 @@ class CompressPlan:
         khost = None
         self._settle()                                   # (a previous pass that returned on its early status words: ANY next
         #                                                   enqueue of the plan reads its final word first, mirrored or not)
+        st = torch.cuda.current_stream(self.device) if stream is None else stream
         if mirror:
             if self._khost is None:
                 self._khost = _khost_get()               # (pinned words from the process-wide pool: never freed)
-                self._khost_addr, self._khost_word, self._khost_final = self._khost.addr, self._khost.word, self._khost.final
-            self._khost_word.value = -1                  # (host write: the previous pass of this plan was finished)
-            self._khost_final.value = 0
-            self._khost.in_flight = True
-            khost = self._khost_addr
-        self._khost_armed = bool(mirror)
+            kh = self._khost
+            kh.word.value = -1                           # (host write: the previous pass of this plan was settled)
+            kh.final.value = 0
+            kh.in_flight = True
+            khost = kh.addr
+        self._armed = st if mirror else None
         with on_device(self.device):
             rc = lib().vc2_compress_ex2(ptr(flat), self.F, self.N, self.D, DTYPE_CODE[self.dtype], self.base_scale,
-                                        self.map_mode, self.grid_h, ptr(src if self.rows is not None else None),
-                                        src.shape[0], ptr(self.ws), self.ws.numel(), ptr(self.rows), ptr(self.idx),
-                                        self.cap, ptr(self.ks), ptr(self.kout), ptr(self.v), ptr(self.f),
+                                        self.map_mode, self.grid_h, ptr(src if o.rows is not None else None),
+                                        src.shape[0], ptr(self.ws), self.ws.numel(), ptr(o.rows), ptr(o.idx),
+                                        self.cap, ptr(o.ks), ptr(o.kout), ptr(o.v), ptr(o.f),
                                         ptr(tail if self.tail_rows else None), self.tail_rows,
-                                        1 if have_stats else 0, khost,
-                                        stream_ptr(self.device) if stream is None else ctypes.c_void_p(stream.cuda_stream))
+                                        1 if have_stats else 0, khost, ctypes.c_void_p(st.cuda_stream))
         if rc != 0 and mirror:                           # (nothing was launched: the mirror block is not in flight)
             self._khost.in_flight = False
-            self._khost_armed = False
+            self._armed = None
         check(rc, "vc2_compress")
 
     def settle_quietly(self) -> None:
@@ -234,8 +273,7 @@ class CompressPlan:
             pass
 
     def __del__(self):
-        if getattr(self, "_late", None) is not None:
-            self.settle_quietly()
+        self.settle_quietly()
         kh = getattr(self, "_khost", None)
         if kh is not None:
             try:
@@ -246,68 +284,55 @@ class CompressPlan:
     def finish(self) -> CompressionResult:
         # (spinning on an event behind a copy to pinned memory instead of this blocking copy: measured, no gain -- torch's
         #  blocking copy already spins)
-        if self._khost_armed:
+        out, st, self._armed = self.out, self._armed, None
+        if st is not None:
             # the count from the pinned mirror: the caller goes on (slicing, the next launches) while the gather launch is
             # still running -- everything it does with these tensors is ordered by the stream, like the reference's
             # tensors after its `.tolist()`.  Falls back to the blocking copy after 50 ms.
-            self._khost_armed = False
-            K = int(lib().vc2_wait_host_count(self._khost_addr, 0.05))
+            kh = self._khost
+            K = int(lib().vc2_wait_host_count(kh.addr, 0.05))
             if K >= 0:
                 # the launch's FINAL status word arrives when its last selection ends (~10 us after K): taken if it is
                 # there already, else this pass is settled before the plan's next one starts (_settle) -- a late
                 # selection-guard hit is raised there, never lost
-                fin = int(self._khost_final.value)
-                if fin & _STATUS_FINAL:
-                    status = fin & ~_STATUS_FINAL
-                else:
-                    status = int(self._khost.t[1])
-                    self._late = (self.kout, self.cap, K)
-                return self._result(self.take(), K, status)
-        K, status = self.kout.tolist()                   # the single host sync of the path
-        return self._result(self.take(), K, status)
+                early, final = _mirror_words(kh)
+                if final is None and not early:
+                    self._late = _LateStatus(kh, self.cap, K, st)
+                    return out.result(K, 0)
+                if final is None:                        # (a fault in the early words, raised here once: the block is
+                    st.synchronize()                     #  quiet before the plan's next pass re-arms it)
+                    final = _mirror_words(kh)[1]
+                return out.result(K, early if final is None else final)
+        K, status = out.kout.tolist()                    # the single host sync of the path
+        return out.result(K, status)
 
     def _settle(self) -> None:
-        """A pass that returned on the early status words of the host mirror: read its final status now (the device word,
-        one blocking copy -- by now the launch is long over) and raise what it reports."""
-        late, self._late = getattr(self, "_late", None), None
-        if late is None:
-            return
-        kout, cap, K = late
-        fin = int(self._khost_final.value) if self._khost is not None else 0
-        status = (fin & ~_STATUS_FINAL) if fin & _STATUS_FINAL else int(kout[1].item())
-        if status:
-            try:
-                _raise_status(status, cap, K)
-            except RuntimeError as e:
-                raise RuntimeError(f"the PREVIOUS pass of this plan (its result was already returned): {e}") from None
-
-    def take(self):
-        """The enqueued pass's output tensors, detached from the plan: the plan can take new outputs and the next clip
-        (same stream: ordered) while this one is still running; `finish_many` reads the counts of a whole batch in one go."""
-        return (self.rows, self.idx, self.ks, self.v, self.f, self.kout, self.cap, self.tail_rows)
-
-    @staticmethod
-    def _result(taken, K, status) -> CompressionResult:
-        rows, idx, ks, v, f, _kout, cap, tail_rows = taken
-        if status:
-            _raise_status(int(status), cap, int(K))
-        return CompressionResult(rows[:K + tail_rows] if rows is not None else None, idx[:K], ks, int(K), v, f)
-
-    @staticmethod
-    def finish_many(taken_list) -> List[CompressionResult]:
-        """Results of several enqueued passes (CompressPlan.take) whose streams have been synchronised: ONE device-to-host
-        copy for all their (K, status) words instead of a sync per clip."""
-        if not taken_list:
-            return []
-        words = torch.stack([t[5] for t in taken_list]).tolist()
-        return [CompressPlan._result(t, K, status) for t, (K, status) in zip(taken_list, words)]
+        """A pass that returned on the early status words of the host mirror: read its final status word now and raise
+        what it reports.  The only reader of the pending record: owner and a thread that evicts the plan claim it under
+        the lock, so that exactly one of them reports it, and the block is read before the owner can re-arm it.  A word
+        that has not arrived yet is waited for on the stream the pass was enqueued on."""
+        with self._settle_lock:
+            p, self._late = self._late, None
+            if p is None:
+                return
+            status = _mirror_words(p.block)[1]
+            if status is None:
+                p.stream.synchronize()
+                status = _mirror_words(p.block)[1]
+        try:
+            if status is None:
+                raise RuntimeError("vidcom2_amd: no final status word after its stream was synchronised -- please report")
+            if status:
+                _raise_status(status, p.cap, p.K)
+        except RuntimeError as e:
+            raise RuntimeError(f"the PREVIOUS pass of this plan (its result was already returned): {e}") from None
 
 
 # ---- plan cache of the one-shot API --------------------------------------------------------------------------
 # `compress()` / `vidcom2_compression()` / the model hooks run one pass per call; building a CompressPlan (a ~30 MB
 # workspace, status words) costs more than a quarter of the pass.  Plans are therefore kept per (shape, dtype, device,
 # options, HIP stream, thread): work enqueued on ONE stream is ordered, so re-using a plan's workspace there is safe;
-# another stream or thread gets its own plan.  Outputs are NOT cached (CompressPlan.new_outputs).
+# another stream or thread gets its own plan.  Outputs are NOT cached (`fresh_outputs`: CompressPlan.new_outputs).
 _PLAN_CACHE: "collections.OrderedDict" = collections.OrderedDict()
 _PLAN_CACHE_MAX = int(os.environ.get("VC2_PLAN_CACHE", "8"))       # 0 disables the cache
 _PLAN_CACHE_BYTES = int(os.environ.get("VC2_PLAN_CACHE_MB", "1024")) << 20   # workspaces + output sets kept alive by the cache
@@ -317,7 +342,8 @@ _EARLY_COUNT = os.environ.get("VC2_EARLY_COUNT", "1") != "0"        # one-shot c
 _PREALLOC = os.environ.get("VC2_PREALLOC", "1") != "0"             # next call's outputs allocated while this pass runs
 
 
-def _cached_plan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores, gather, tail_rows) -> "CompressPlan":
+def _cached_plan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores, gather, tail_rows,
+                 fresh_outputs: bool = False) -> "CompressPlan":
     device = torch.device(device)
     if device.index is None:
         device = torch.device(device.type, torch.cuda.current_device())
@@ -340,9 +366,9 @@ def _cached_plan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores
                 while len(_PLAN_CACHE) > _PLAN_CACHE_MAX or \
                         (len(_PLAN_CACHE) > 1 and sum(p.cached_bytes() for p in _PLAN_CACHE.values()) > _PLAN_CACHE_BYTES):
                     evicted.append(_PLAN_CACHE.popitem(last=False)[1])
-            for old in evicted:               # (outside the lock: may read a device word)
+            for old in evicted:               # (outside the lock: may wait for another thread's stream)
                 old.settle_quietly()          # a pass that returned on its early status words gets its last word here
-    else:
+    elif fresh_outputs:
         plan.new_outputs()
     return plan
 
@@ -362,14 +388,20 @@ class _KHost:
     """Four pinned int64 words for vc2_compress_ex2's host mirror (K, early status, final status | 2^62, spare).  Pooled
     and never freed: the selection launch writes the final word ~10 us after the count, possibly after the plan that
     enqueued the pass is gone -- a block handed back to the allocator could be somebody else's memory by then."""
-    __slots__ = ("t", "addr", "word", "final", "in_flight")
+    __slots__ = ("t", "addr", "word", "early", "final", "in_flight")
 
     def __init__(self):
         self.t = torch.zeros(4, dtype=torch.int64).pin_memory()
         self.addr = ctypes.c_void_p(self.t.data_ptr())
-        self.word = ctypes.c_int64.from_address(self.t.data_ptr())
-        self.final = ctypes.c_int64.from_address(self.t.data_ptr() + 16)
+        self.word, self.early, self.final = (ctypes.c_int64.from_address(self.t.data_ptr() + 8 * i) for i in range(3))
         self.in_flight = False
+
+
+def _mirror_words(b: _KHost) -> Tuple[int, Optional[int]]:
+    """(early status, final status -- None while the launch has not written it) of a mirror block: every read of a
+    pass's status from these words goes through here (the tests replace it to force the late path)."""
+    fin = b.final.value
+    return b.early.value, (fin & ~_STATUS_FINAL if fin & _STATUS_FINAL else None)
 
 
 _KHOST_LOCK = threading.RLock()       # (re-entrant: a garbage collection inside the locked region may finalise a plan -> _khost_put)
@@ -475,7 +507,8 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
         plan = CompressPlan(R // tpf, tpf, D, x.dtype, x.device, base_scale, mapper, grid_h, want_scores, gather,
                             tail_rows=ntail, ws=stats_ws)
     else:
-        plan = _cached_plan(R // tpf, tpf, D, x.dtype, x.device, base_scale, mapper, grid_h, want_scores, gather, ntail)
+        plan = _cached_plan(R // tpf, tpf, D, x.dtype, x.device, base_scale, mapper, grid_h, want_scores, gather, ntail,
+                            fresh_outputs=True)
     plan.enqueue(x, src, tail, have_stats=stats_ws is not None, mirror=_EARLY_COUNT)
     if stats_ws is None and _PREALLOC and _PLAN_CACHE_MAX > 0 and plan.output_bytes() <= _SPARE_MAX_BYTES:
         plan.prepare_spare()              # (the GPU is busy for the next ~190 us: the next call's outputs cost nothing here)
@@ -487,23 +520,18 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     return res
 
 
-_LANES: dict = {}
-_LANES_LOCK = threading.Lock()
+_LANES = threading.local()              # per thread: {device index: [streams]}
 
 
 def _lane_streams(dev: torch.device, n: int):
-    """The n extra streams compress_batch runs clips on -- created once per (device, thread) and kept: the plan cache is
-    keyed by stream, so fresh streams per call meant fresh plans (and workspaces) per call: 0.5-1.2 ms of set-up per batch."""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), threading.get_ident())
-    with _LANES_LOCK:
-        if key not in _LANES:                 # a new thread: drop the lanes of threads that have ended
-            alive = {t.ident for t in threading.enumerate()}
-            for k in [k for k in _LANES if k[1] not in alive]:
-                del _LANES[k]
-        lst = _LANES.setdefault(key, [])
-        while len(lst) < n:
-            lst.append(torch.cuda.Stream(dev))
-        return lst[:n]
+    """The n extra streams compress_batch runs clips on -- created once per (thread, device) and kept for as long as the
+    thread lives: the plan cache is keyed by stream, so fresh streams per call meant fresh plans (and workspaces) per
+    call: 0.5-1.2 ms of set-up per batch."""
+    by_dev = _LANES.__dict__.setdefault("by_dev", {})
+    lst = by_dev.setdefault(dev.index if dev.index is not None else torch.cuda.current_device(), [])
+    while len(lst) < n:
+        lst.append(torch.cuda.Stream(dev))
+    return lst[:n]
 
 
 BATCH_LANES = 3          # compress_batch's default: clips in flight (16 cfg5 clips: 254 / 216 / 203 / 197 us per clip with 1 / 2 / 3 / 4)
@@ -550,76 +578,54 @@ def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool,
             raise RuntimeError(f"clip {i}: shape {tuple(x.shape)} is not [frames * {t}, dim]")
     cur = torch.cuda.current_stream(dev)
     lanes = [cur] + _lane_streams(dev, max(1, min(int(in_flight), len(clips))) - 1)
+    plans = {}
+
+    def plan_on(j, x, t):                 # lane j's cached plan for x's shape (its workspace: work on a stream is ordered)
+        key = (j, x.shape, x.dtype, t)
+        if key not in plans:
+            with torch.cuda.stream(lanes[j]):
+                plans[key] = _cached_plan(x.shape[0] // t, t, x.shape[1], x.dtype, dev, base_scale, "linear", 0, False,
+                                          gather, 0)
+        return plans[key]
+
+    # Clips of one shape (the batched-eval case, BASELINE config 5): ONE allocation per output kind for the whole batch --
+    # each clip's pass writes its slice -- on the caller's stream.  Round 4 looked a plan up, allocated six tensors and
+    # recorded them on the caller's stream PER CLIP: ~100 us of host work per clip, more than the 75 us a lane's share of
+    # the GPU time leaves -- 16 clips took 5.8 ms, slower than one at a time.
     same = all(c.shape == clips[0].shape and c.dtype == clips[0].dtype and c.device == dev for c in clips) \
         and all(t == tpfs[0] for t in tpfs)
-    if not same:
-        return _compress_batch_mixed(clips, tpfs, base_scale, lanes, gather)
-    tpf = tpfs[0]
-    # Clips of one shape (the batched-eval case, BASELINE config 5): ONE plan per lane (workspace; work on a stream is
-    # ordered), ONE allocation per output kind for the whole batch -- each clip's pass writes its slice --, one
-    # device-to-host copy for all the counts at the end.  Round 4 looked a plan up, allocated six tensors and recorded
-    # them on the caller's stream PER CLIP: ~100 us of host work per clip, more than the 75 us a lane's share of the GPU
-    # time leaves -- 16 clips took 5.8 ms, slower than one at a time.
-    n, x0 = len(clips), clips[0]
-    F_, D_ = x0.shape[0] // int(tpf), x0.shape[1]
-    plans = []
-    for st in lanes:
-        with torch.cuda.stream(st):
-            plans.append(_cached_plan(F_, int(tpf), D_, x0.dtype, dev, base_scale, "linear", 0, False, gather, 0))
-    p0 = plans[0]
-    idx_all = torch.empty((n, p0.cap), dtype=torch.int64, device=dev)
-    ks_all = torch.empty((n, F_), dtype=torch.int64, device=dev)
-    rows_all = torch.empty((n, p0.cap, D_), dtype=x0.dtype, device=dev) if gather else None
-    kout_all = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    batch = plan_on(0, clips[0], tpfs[0])._alloc_outputs(len(clips)) if same else None
     for st in lanes[1:]:
-        st.wait_stream(cur)               # inputs and these buffers belong to the caller's stream
-    # (no record_stream on the batch's buffers: every lane is joined into the caller's stream below, before this function
-    #  returns -- whatever the caller does with them, freeing included, is ordered behind the lanes' work)
-    for i, x in enumerate(clips):
-        plan = plans[i % len(lanes)]
-        plan.idx, plan.ks, plan.rows, plan.v, plan.f, plan.kout = idx_all[i], ks_all[i], (rows_all[i] if gather else None), None, None, kout_all[i]
-        plan.enqueue(x, stream=lanes[i % len(lanes)])
+        st.wait_stream(cur)               # inputs and the batch's buffers belong to the caller's stream
+    outs = []
+    for i, (x, t) in enumerate(zip(clips, tpfs)):
+        j = i % len(lanes)
+        plan = plan_on(j, x, t)
+        if batch is not None:
+            # (no record_stream on the batch's buffers: every lane is joined into the caller's stream below, before this
+            #  function returns -- whatever the caller does with them, freeing included, is ordered behind the lanes' work)
+            out = OutputSet(*(None if b is None else b[i] for b in batch))
+        else:
+            with torch.cuda.stream(lanes[j]):     # fresh per clip, allocated (and owned) on the lane's stream ...
+                out = plan._alloc_outputs()
+            if j:                                 # ... and consumed on the caller's
+                for tn in out:
+                    if tn is not None:
+                        tn.record_stream(cur)
+        plan.enqueue(x, stream=lanes[j], out=out)
+        outs.append(out)
     for st in lanes[1:]:
         cur.wait_stream(st)               # results are safe to use on the current stream
-    for plan in plans:
-        plan.new_outputs()                # (the cached plans must not keep pointing into the batch's buffers)
-    words = kout_all.tolist()             # the single host sync of the batch
-    out = []
-    for i, (K, status) in enumerate(words):
-        if status:
-            _raise_status(int(status), p0.cap, int(K))
-    _check_budgets(ks_all, int(tpf), x0.dtype)
-    for i, (K, status) in enumerate(words):
-        rows_i, idx_i, ks_i = (rows_all[i, :K] if gather else None), idx_all[i, :K], ks_all[i]
+    words = (batch.kout if batch is not None else torch.stack([o.kout for o in outs])).tolist()   # the single host sync
+    res = [o.result(K, status) for o, (K, status) in zip(outs, words)]
+    if batch is not None:
+        _check_budgets(batch.ks, tpfs[0], clips[0].dtype)
         if own_storage:
-            rows_i, idx_i, ks_i = (rows_i.clone() if gather else None), idx_i.clone(), ks_i.clone()
-        out.append(CompressionResult(rows_i, idx_i, ks_i, int(K), None, None))
-    return out
-
-
-def _compress_batch_mixed(clips, tpfs: List[int], base_scale: float, lanes, gather: bool):
-    """compress_batch for clips of different shapes (or tokens per frame): a plan lookup and fresh outputs per clip."""
-    dev = clips[0].device
-    cur = lanes[0]
-    for st in lanes[1:]:
-        st.wait_stream(cur)                               # inputs were produced on the current stream
-    taken = []
-    for i, x in enumerate(clips):
-        st = lanes[i % len(lanes)]
-        with torch.cuda.stream(st):       # the plan's buffers are allocated (and owned) on the lane's stream
-            plan = _cached_plan(x.shape[0] // tpfs[i], tpfs[i], x.shape[1], x.dtype, dev, base_scale, "linear", 0,
-                                False, gather, 0)
-            plan.enqueue(x)
-            taken.append(plan.take())
-            if st is not cur:             # allocated on the lane's stream, consumed on the caller's
-                for t in taken[-1][:6]:
-                    if t is not None:
-                        t.record_stream(cur)
-    for st in lanes[1:]:
-        cur.wait_stream(st)                               # results are safe to use on the current stream
-    res = CompressPlan.finish_many(taken)
-    for r, n, x in zip(res, tpfs, clips):
-        _check_budgets(r.ks, n, x.dtype)
+            res = [CompressionResult(None if r.rows is None else r.rows.clone(), r.global_idx.clone(), r.ks.clone(), r.K)
+                   for r in res]
+    else:
+        for r, t, x in zip(res, tpfs, clips):
+            _check_budgets(r.ks, t, x.dtype)
     return res
 
 
