@@ -88,6 +88,34 @@ template <int DT> __device__ __forceinline__ void stT(void* p, int64_t i, float 
   }
 }
 
+// ---- stores of the sweeps' bulk partials -----------------------------------------------
+// What a sweep leaves for the NEXT launch (sweep 1's part[G][2][D], sweep 2's part and bsum): megabytes that no workgroup
+// of the same launch reads and whose readers run on all eight XCDs, so keeping them dirty in the writer's L2 buys nothing:
+// plain stores leave them there until the kernel boundary writes them back.  The bits stored and the order of every sum
+// do not depend on the store form; the readers are ordered by the kernel boundary.  Forms measured against each other at
+// the target shape as builds of the whole library (NOTES_r07.md): plain, 8-byte write-through (agent-scope atomic
+// stores), 8- and 16-byte non-temporal, 16-byte write-through.  Kept: 16-byte write-through for the fp64 partials,
+// non-temporal for sweep 2's fp32 block sums.
+//
+// Two adjacent fp64 words (p: 16-byte aligned) in ONE write-through store.  Rests on two rows of the hardware guide's
+// price list: "boundary" (a dependent kernel boundary costs B / 6 TB/s more when its predecessor leaves B bytes dirty) and
+// "publish-large" (tens of KB per workgroup from a short epilogue: write-through stores beat plain stores + a release;
+// narrow write-through stores cost 2.7x a 16-byte one per byte).  The A/B that chose it: k_chan_stats 31.3 -> 30.2 us,
+// k_norm_colsum2 32.8 -> 31.8 us, the pass 171.5 -> 169.7 us against plain stores (NOTES_r07.md).  A single instruction
+// with no builtin for a plain pointer; the s_nop keeps the compiler's next instruction off the data registers until
+// the store has read them.
+__device__ __forceinline__ void store_partial2(double* p, double a, double b) {
+  typedef double d2_t __attribute__((ext_vector_type(2)));
+  const d2_t v = {a, b};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
+}
+// A pair of fp32 block sums (p: 8-byte aligned), non-temporal: written once per 16 rows from inside the row loop.
+__device__ __forceinline__ void store_bsum(float* p, f2_t v) {
+  union { f2_t f; unsigned long long u; } c;
+  c.f = v;
+  __builtin_nontemporal_store(c.u, reinterpret_cast<unsigned long long*>(p));
+}
+
 // ---- 16-byte vector of VEC elements, unpacked to fp32 --------------------------------
 // VEC == Tr<DT>::VEC : one 16-byte load per lane (coalesced 1 KiB per wave);
 // VEC == 1           : scalar fallback for rows whose byte length is not a multiple of 16.

@@ -58,9 +58,15 @@ __device__ __forceinline__ void dbg_stamp(int tag) {      // (one lane) wall clo
 namespace vc2 { __device__ unsigned long long g_dbg_wg[8][2][4096]; }
 namespace vc2 { __device__ unsigned long long g_dbg_vc[6][4096]; }        // k_video_centre (scripts/dev/vc_waves.py): see there     // (slots 4, 5: sweep 2's first row landed / row loops over, combine done)
 #define VC2_WGTIME(slot, which) do { if (threadIdx.x == 0 && blockIdx.x < 4096) g_dbg_wg[slot][which][blockIdx.x] = wall_clock64(); } while (0)
+// the drain of sweeps 1 and 2 (scripts/dev/s0_drain.py): 0 / 1 k_chan_stats begin / end per workgroup, 2 k_var_select's variance
+// workgroups begin, 3 k_frame_centres' frame workgroups begin, 4 / 5 / 6 the hardware id (HW_REG_HW_ID) of k_dist's / sweep 2's / sweep 1's workgroups
+namespace vc2 { __device__ unsigned long long g_dbg_s0[8][4096]; }
+#define VC2_S0(slot, idx, val) do { if (threadIdx.x == 0 && (idx) < 4096) g_dbg_s0[slot][idx] = (val); } while (0)
+#define VC2_HWID() ((unsigned long long)__builtin_amdgcn_s_getreg((4 /*HW_ID*/) | (0 << 6) | (31 << 11)) | ((unsigned long long)__builtin_amdgcn_s_getreg((20 /*XCC_ID*/) | (0 << 6) | (3 << 11)) << 32))
 #else
 #define VC2_STAMP(tag) ((void)0)
 #define VC2_WGTIME(slot, which) ((void)0)
+#define VC2_S0(slot, idx, val) ((void)0)
 #endif
 
 #include "vc2_select2.h"        // (after the debug macros: the selection rounds carry stamps in debug builds)
@@ -184,13 +190,19 @@ __global__ __launch_bounds__(kStatsWaves * 64) void k_chan_stats(const void* __r
                                                                  int D, int CV, int N, int splits,
                                                                  int rows_per_group, int block_frames,
                                                                  double* __restrict__ part, PoolSrc pool,
-                                                                 uint32_t* __restrict__ var_reset = nullptr) {
+                                                                 uint32_t* __restrict__ var_reset = nullptr,
+                                                                 int slab_lanes = 64) {
   __shared__ double sm[kStatsWaves][2 * VEC][64];
   // (the pass's variance array back to "not written yet" for k_var_select, which polls it inside its own launch)
   if (var_reset && blockIdx.x == 0 && blockIdx.y == 0) for (int i = threadIdx.x; i < D; i += kStatsWaves * 64) var_reset[i] = 0xFFFFFFFFu;
+  VC2_S0(0, blockIdx.y * gridDim.x + blockIdx.x, wall_clock64());
+#ifdef VC2_DEBUG_TIMING
+  VC2_S0(6, blockIdx.y * gridDim.x + blockIdx.x, VC2_HWID());
+#endif
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int cv = blockIdx.x * 64 + lane;
-  const bool active = cv < CV;
+  // a slab is slab_lanes (<= 64) column vectors wide: the other lanes of the waves idle (Plan::stat_lanes)
+  const int cv = blockIdx.x * slab_lanes + lane;
+  const bool active = lane < slab_lanes && cv < CV;
   const int64_t frame = int64_t(blockIdx.y) / splits;
   const int64_t r0 = frame * N + int64_t(blockIdx.y % splits) * rows_per_group;
   const int64_t r1 = min(min(R, (frame + 1) * N), r0 + rows_per_group);
@@ -246,17 +258,34 @@ __global__ __launch_bounds__(kStatsWaves * 64) void k_chan_stats(const void* __r
   __syncthreads();
   // all four waves add the four wave sums (wave order: fixed) and store with consecutive threads on consecutive
   // columns of the slab: the slab's 64 * VEC columns, sums first, then squares
-  const int64_t c0 = int64_t(blockIdx.x) * 64 * VEC;
-  for (int t = threadIdx.x; t < 2 * 64 * VEC; t += kStatsWaves * 64) {
-    const int which = t / (64 * VEC), lc = t % (64 * VEC);
-    const int l = lc / VEC, j = lc % VEC;
-    if (c0 + lc < D) {
-      double a = 0.0;
+  const int64_t c0 = int64_t(blockIdx.x) * slab_lanes * VEC;
+  // The partials go out write-through (store_partial2: they leave the L2 as they are written, the kernel boundary has
+  // nothing left to write back), 16 bytes per thread: two adjacent columns each (D % VEC == 0: a pair lies inside the
+  // row or outside it).  The scalar fallback keeps its plain stores.
+  if constexpr (VEC % 2 == 0) {
+    for (int t = 2 * threadIdx.x; t < 2 * 64 * VEC; t += 2 * kStatsWaves * 64) {
+      const int which = t / (64 * VEC), lc = t % (64 * VEC);
+      const int l = lc / VEC, j = lc % VEC;
+      if (l < slab_lanes && c0 + lc < D) {
+        double a = 0.0, b = 0.0;
 #pragma unroll
-      for (int w = 0; w < kStatsWaves; ++w) a += sm[w][which * VEC + j][l];
-      part[(int64_t(blockIdx.y) * 2 + which) * D + c0 + lc] = a;
+        for (int w = 0; w < kStatsWaves; ++w) { a += sm[w][which * VEC + j][l]; b += sm[w][which * VEC + j + 1][l]; }
+        store_partial2(part + (int64_t(blockIdx.y) * 2 + which) * D + c0 + lc, a, b);
+      }
+    }
+  } else {
+    for (int t = threadIdx.x; t < 2 * 64 * VEC; t += kStatsWaves * 64) {
+      const int which = t / (64 * VEC), lc = t % (64 * VEC);
+      const int l = lc / VEC, j = lc % VEC;
+      if (l < slab_lanes && c0 + lc < D) {
+        double a = 0.0;
+#pragma unroll
+        for (int w = 0; w < kStatsWaves; ++w) a += sm[w][which * VEC + j][l];
+        part[(int64_t(blockIdx.y) * 2 + which) * D + c0 + lc] = a;
+      }
     }
   }
+  VC2_S0(1, blockIdx.y * gridDim.x + blockIdx.x, wall_clock64());
 }
 
 // Level 1: per stat block b (kStatBlockFrames frames; the last one may be shorter) the fixed-order sum of its
@@ -692,6 +721,7 @@ __global__ __launch_bounds__(kSelNT) void k_var_select(VarSelArgs a) {
   if (threadIdx.x >= VT) return;
   const int vb = int(blockIdx.x) - 1, nvt = (int(gridDim.x) - 1) * VT, vt = vb * VT + int(threadIdx.x);
   if (vb == 0 && threadIdx.x == 0) VC2_STAMP(100);
+  VC2_S0(2, vb, wall_clock64());
   if (a.kstatus && vt == 0) *a.kstatus = 0ull;                     // K_out[1]: k_select ORs its bits in
   if (a.fixq) for (int i = vt; i < a.nfixq; i += nvt) a.fixq[i] = 0ull;
   var_from_stats_body<DT, CW, true>(nullptr, a.NB, a.n_each, a.n_last, a.D, nullptr, a.var_f32, a.ps, a.ft, vb, int(threadIdx.x), sm);
@@ -1555,6 +1585,9 @@ __global__ __launch_bounds__(kRowWaves * 64, kS2Waves) void k_norm_colsum2(const
   const int bid = int(blockIdx.x) - nrider;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+#ifdef VC2_DEBUG_TIMING
+  VC2_S0(5, blockIdx.x, VC2_HWID());
+#endif
   // (rows fit 31 bits: the launch checks R < 2^31; 32-bit uniform arithmetic keeps the index math in a few SALU instructions)
   const int Rr = int(R);
   // ORD (round 5, frames of N <= 512 tokens): the frame means in TORCH'S OWN ORDER, natively.  Workgroup `bid` = piece
@@ -1789,7 +1822,7 @@ __global__ __launch_bounds__(kRowWaves * 64, kS2Waves) void k_norm_colsum2(const
           const int blk = ib < 0 ? ord_b0 + (i >> 4) : nblk;
           float* dst = bsum + (size_t(uint32_t(f * (nblk + 1) + blk))) * C + 2 * lane;
 #pragma unroll
-          for (int k = 0; k < NP; ++k) *reinterpret_cast<f2_t*>(dst + 128 * k) = chain[k];
+          for (int k = 0; k < NP; ++k) store_bsum(dst + 128 * k, chain[k]);
         }
       }
     }
@@ -1807,13 +1840,14 @@ __global__ __launch_bounds__(kRowWaves * 64, kS2Waves) void k_norm_colsum2(const
 #pragma unroll
       for (int i = 0; i < PER; ++i) scratch[(wave * PER + i) * 64 + lane] = acc[h * PER + i];
       __syncthreads();
-      // scratch[w][i][l] = wave w's sum of the lane-l compact position of slot h PER + i
-      for (int t = tid; t < PER * 64; t += kRowWaves * 64) {
-        const int i = t >> 6, l = t & 63;
-        double v = scratch[t];
+      // scratch[w][i][l] = wave w's sum of the lane-l compact position of slot h PER + i.  Write-through, like sweep 1's.
+      static_assert(PER % 2 == 0, "slots 2 k, 2 k + 1 are a lane's two adjacent compact positions");
+      for (int t = tid; t < (PER / 2) * 64; t += kRowWaves * 64) {  // a thread: both words of one pair, 16 bytes
+        const int i = 2 * (t >> 6), l = t & 63;
+        double v0 = scratch[i * 64 + l], v1 = scratch[(i + 1) * 64 + l];
 #pragma unroll
-        for (int w = 1; w < kRowWaves; ++w) v += scratch[w * PER * 64 + t];
-        part[size_t(uint32_t(f * S + sp)) * C + compact_pos<1>(h * PER + i, l)] = v;
+        for (int w = 1; w < kRowWaves; ++w) { v0 += scratch[(w * PER + i) * 64 + l]; v1 += scratch[(w * PER + i + 1) * 64 + l]; }
+        store_partial2(part + size_t(uint32_t(f * S + sp)) * C + compact_pos<1>(h * PER + i, l), v0, v1);
       }
     }
     seg_a = seg_b;
@@ -2265,6 +2299,7 @@ __global__ __launch_bounds__(64 * kCentreFL) void k_frame_centres(const double* 
 #ifdef VC2_DEBUG_TIMING
   if (tid == 0 && blockIdx.x == 0 && blockIdx.y == fy) g_dbg_wg[5][0][4095] = wall_clock64();     // (a frame workgroup's begin: the launch's clock zero)
 #endif
+  VC2_S0(3, (int(blockIdx.y) - fy) * int(gridDim.x) + int(blockIdx.x), wall_clock64());
   const int c = blockIdx.x * 64 + cl;
   const int g = int(blockIdx.y) - fy;
   const int FGn = int(gridDim.y) - fy;                           // frame groups of this launch
@@ -3013,6 +3048,9 @@ __global__ __launch_bounds__(kRowWaves * 64, 1) void k_dist(const void* __restri
   int n = n0 + wave;
   if (tid == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1)) VC2_STAMP(700);
   VC2_WGTIME(2, 0);
+#ifdef VC2_DEBUG_TIMING
+  VC2_S0(4, blockIdx.x, VC2_HWID());
+#endif
   // (unused, kept on purpose: the extra use of this offset steers the optimiser to the instruction sequence every k_dist
   //  instantiation has been measured with -- without it the register allocation moves, e.g. 109 -> 107 VGPRs)
   const size_t row0_bytes = (size_t(f) * N + n) * (size_t(D) * ES);
@@ -4400,6 +4438,7 @@ struct Plan {
   int64_t F, N, D, R;
   int dt, ES, VEC, CV, TPB;     // VEC actually used (1 = scalar fallback), column vectors, threads
   int G, rows_per_group;        // sweep-1 row groups (G = F * stat_splits), stat blocks
+  int stat_lanes;               // sweep 1: column vectors per slab, i.e. lanes of a wave at work (<= 64)
   int stat_splits, NB, BF;      // groups per frame; stat blocks of BF (<= kStatBlockFrames) frames
   int64_t F_total;              // frames of the WHOLE video (frame-sharded pass: canonical blockings depend on it)
   int ord_S, ord_m;             // sweep 2, ORD form (k_norm_colsum2<.., ORD>): frames [0, ord_nA) are swept by ord_S - 1 workgroups each, the
@@ -4457,6 +4496,18 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
   p->rows_per_group = int(cdiv(N, p->stat_splits));
   p->stat_splits = int(cdiv(N, p->rows_per_group));
   p->G = int(F * p->stat_splits);
+  // Sweep 1's workgroups (one per group and slab of columns) are all resident when there are at most 4 per CU (1024), and
+  // the launch lasts as long as its fullest CU: 7 slabs of 64 lanes x 128 groups = 896 workgroups leave half of the CUs
+  // with 4 of them and half with 3.  Narrower slabs that fill every CU alike -- 8 slabs of 56 lanes = 1024 workgroups,
+  // 4 x 56 instead of 4 x 64 column vectors on the fullest CU -- are faster although an eighth of the lanes idles
+  // (k_chan_stats 32.5 -> 31.3 us at the target shape, NOTES_r07.md).  Which thread sweeps a column changes nothing
+  // about its sums: the same rows in the same order, the same wave combine.
+  p->stat_lanes = 64;
+  if (p->VEC > 1) {
+    auto busiest = [&](int l) { return cdiv(int64_t(p->G) * cdiv(p->CV, l), 256) * l; };   // column vectors on the fullest CU
+    for (int l = 56; l >= 32; l -= 8)
+      if (int64_t(p->G) * cdiv(p->CV, l) <= 1024 && busiest(l) < busiest(p->stat_lanes)) p->stat_lanes = l;
+  }
   p->BF = block_frames > 0 ? std::min(block_frames, kStatBlockFrames) : kStatBlockFrames;
   p->NB = int(cdiv(F, p->BF));
   // sweep 2 runs as ONE wave of workgroups: 2 per CU fit (LDS row buffers, VGPRs) = 512 slots on 256 CUs, and every
@@ -4610,16 +4661,16 @@ int need_ws(const Plan& p, void* ws, size_t ws_bytes) {
 int launch_stats_sweep(const Plan& p, const void* x, void* ws, const PoolSrc& pool, hipStream_t st, uint32_t* var_reset = nullptr) {
   double* part = wsp<double>(ws, p.o_part_stats);
   if (p.G > 65535) return fail(VC2_ERR_UNSUPPORTED, "too many sweep-1 row groups (%d)", p.G);
-  dim3 grid(unsigned(cdiv(p.CV, 64)), unsigned(p.G));
+  dim3 grid(unsigned(cdiv(p.CV, p.stat_lanes)), unsigned(p.G));
   ProfScope ps_(KID_STATS, st);
   if (pool.xin) {
     VC2_DISPATCH_VEC(p, hipLaunchKernelGGL((k_chan_stats<DT, VEC, 8, 1>), grid, dim3(kStatsWaves * 64), 0, st, x,
                                             p.R, int(p.D), p.CV, int(p.N), p.stat_splits, p.rows_per_group, p.BF, part,
-                                            pool));
+                                            pool, nullptr, p.stat_lanes));
   } else {
     VC2_DISPATCH_VEC(p, hipLaunchKernelGGL((k_chan_stats<DT, VEC, 8, 0>), grid, dim3(kStatsWaves * 64), 0, st, x,
                                             p.R, int(p.D), p.CV, int(p.N), p.stat_splits, p.rows_per_group, p.BF, part,
-                                            pool, var_reset));
+                                            pool, var_reset, p.stat_lanes));
   }
   return check_launch("chan_stats");
 }
@@ -5868,6 +5919,10 @@ int vc2_debug_wg(unsigned long long* out /*[8][2][4096]*/) {
   (void)hipDeviceSynchronize();
   (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(vc2::g_dbg_wg), sizeof(unsigned long long) * 8 * 2 * 4096);
   return 0;
+}
+int vc2_debug_s0(unsigned long long* out /*[8][4096]*/) {      // the drain stamps (scripts/dev/s0_drain.py)
+  (void)hipDeviceSynchronize();
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(vc2::g_dbg_s0), sizeof(unsigned long long) * 8 * 4096) == hipSuccess ? 0 : -1;
 }
 int vc2_debug_vc(unsigned long long* out) {      // [6][4096]: k_video_centre's per-wave stamps (scripts/dev/vc_waves.py)
   (void)hipDeviceSynchronize();
