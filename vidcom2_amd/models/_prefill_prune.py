@@ -22,6 +22,12 @@ device path (`fused.keep_positions_batched` + `fused.repad_rows`) reproduces it 
 the UNPRUNED mask during the decode steps that follow, while the KV cache holds the pruned layout: `run_decode_step`
 maps the mask that reaches the language model onto that layout (the positions need no change: generate derives them
 from the unpruned mask and `rope_deltas`, i.e. from each row's valid length, as for the row alone).
+
+`renumber=True` (the transformers LLaVA hooks, `llava_hf.py`) is the other position contract: the reference prunes LLaVA
+prompts BEFORE positions exist, so the pruned prompt is numbered 0 .. S'-1 and decoding continues at S'.  A 2-D
+`position_ids [B, S]` then leaves with every kept position lowered by the number of that row's dropped tokens before it
+(B > 1: the batched layout's `text_row0` plane), absent positions stay absent, and the decode layout carries the row's
+dropped count, which `run_decode_step` subtracts from the positions generate derives from the unpruned mask.
 """
 from __future__ import annotations
 
@@ -51,6 +57,7 @@ class _DecodeLayout(NamedTuple):
     mask: torch.Tensor          # [B, S'] pruned 2-D mask of the prefill
     keep: torch.Tensor          # [B, S'] kept positions (-1: pad slot)
     S: int                      # unpruned prompt length
+    dropped: Optional[torch.Tensor] = None      # [B] tokens dropped per row (renumbered positions only)
 
 
 _WARNED: set = set()
@@ -189,11 +196,12 @@ class _LanguageModelShim:
     (attributes, sub-modules, config) is the real module's."""
 
     def __init__(self, real, state: PruneState, choose: Callable[[torch.Tensor], Optional[torch.Tensor]],
-                 choose_many: Optional[Callable[[torch.Tensor], torch.Tensor]] = None):
+                 choose_many: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, renumber: bool = False):
         object.__setattr__(self, "_real", real)
         object.__setattr__(self, "_state", state)
         object.__setattr__(self, "_choose", choose)
         object.__setattr__(self, "_choose_many", choose_many)
+        object.__setattr__(self, "_renumber", renumber)
 
     def __getattr__(self, name):
         return getattr(object.__getattribute__(self, "_real"), name)
@@ -234,7 +242,13 @@ class _LanguageModelShim:
                     kwargs["attention_mask"] = ({k: _prune_attention(v, keep) for k, v in am.items()}
                                                 if isinstance(am, dict) else _prune_attention(am, keep))
                 pos = kwargs.get("position_ids")
-                if torch.is_tensor(pos):
+                if self._renumber:
+                    if torch.is_tensor(pos) and pos.dim() == 2:
+                        # the pruned prompt is numbered as if the dropped tokens had never been there
+                        kp = keep.to(pos.device)
+                        before = kp - torch.arange(kp.numel(), device=kp.device)
+                        kwargs["position_ids"] = pos[:, kp] - before.to(pos.dtype)
+                elif torch.is_tensor(pos):
                     pos = pos[..., keep.to(pos.device)]
                     if pos.dim() == 3 and pos.shape[0] == 4:
                         # transformers >= 4.5x prepends a row of TEXT positions that the decoder only uses to
@@ -304,12 +318,12 @@ class _LanguageModelShim:
             pos_in = pos.to(embeds.device)
             if pos_in.dim() == 2:
                 pos_in, squeeze = pos_in[None], True
-            text_row0 = pos_in.shape[0] == 4
+            text_row0 = pos_in.shape[0] == 4 or (self._renumber and squeeze)
             if pos_in.is_floating_point() and not text_row0:
                 # Qwen3-Omni's TMRoPE positions are fp32 and may be fractional.  Without text_row0 the layout only copies
                 # position values (pad value 0 = the bits of 0.0), so they travel exactly as the 64-bit words of an fp64
                 pos_in, as_bits = pos_in.to(torch.float64).view(torch.int64), True
-        elif pos is None and "position_ids" in kwargs:
+        elif pos is None and "position_ids" in kwargs and not self._renumber:
             # the positions the batch-1 path builds for the row alone (text 0.., rope = position in the unpadded row)
             base = torch.where(am64 != 0, am64.cumsum(1) - 1, torch.zeros((), dtype=torch.int64, device=embeds.device))
             pos_in, text_row0 = base[None].expand(4, B, S), True
@@ -344,7 +358,7 @@ class _LanguageModelShim:
         if vpm is not None:
             kwargs["visual_pos_masks"] = _gather_slots(vpm, keep, False)
         st.kept_video, st.keep_token_indices, st.lengths, st.pruned = kept, keep, lay.lengths, True
-        st.decode = _DecodeLayout(mask, keep, S)
+        st.decode = _DecodeLayout(mask, keep, S, S - lay.lengths if self._renumber else None)
 
 
 def decode_state(model, clear: bool = False) -> Optional[_DecodeLayout]:
@@ -372,6 +386,11 @@ class _DecodeShim:
             past = int(cache.get_seq_length())
             kwargs["attention_mask"] = _map_decode_mask(kwargs.get("attention_mask"), self._dec, past, embeds.shape[1],
                                                         embeds.shape[0])
+            dropped, pos = self._dec.dropped, kwargs.get("position_ids")
+            if dropped is not None and torch.is_tensor(pos) and pos.dim() == 2 and pos.shape[0] % dropped.shape[0] == 0:
+                # generate counts on from the UNPRUNED prompt's last position; the pruned one ended `dropped` earlier
+                dropped = dropped.repeat_interleave(pos.shape[0] // dropped.shape[0], 0)
+                kwargs["position_ids"] = pos - dropped.to(device=pos.device, dtype=pos.dtype)[:, None]
         return self._real(*args, **kwargs)
 
 
@@ -382,10 +401,11 @@ def run_decode_step(model, forward: Callable, lm_attr: str = "language_model"):
 
 def run_with_pruning(model, forward: Callable, choose: Callable[[torch.Tensor], Optional[torch.Tensor]],
                      lm_attr: str = "language_model",
-                     choose_many: Optional[Callable[[torch.Tensor], torch.Tensor]] = None):
+                     choose_many: Optional[Callable[[torch.Tensor], torch.Tensor]] = None, renumber: bool = False):
     """Run `forward()` with the interceptors in place.  `choose(video_embeds)` returns the sorted
     kept indices into the video token list (or None to leave the prompt alone); `choose_many` the same for a batch of
-    B > 1 prompts (None: such batches are left alone)."""
+    B > 1 prompts (None: such batches are left alone); `renumber`: positions as if the dropped tokens had never been in the
+    prompt (module docstring)."""
     state = PruneState()
     mask_inner = model.get_placeholder_mask
 
@@ -398,7 +418,7 @@ def run_with_pruning(model, forward: Callable, choose: Callable[[torch.Tensor], 
             state.video_mask, state.video_embeds = st_mask.bool(), feats
         return out
 
-    shim = _LanguageModelShim(getattr(model, lm_attr), state, choose, choose_many)
+    shim = _LanguageModelShim(getattr(model, lm_attr), state, choose, choose_many, renumber)
     with shadow(model, get_placeholder_mask=get_placeholder_mask, **{lm_attr: shim}):
         out = forward()
     model.__dict__["_vidcom2_last"] = state
