@@ -152,6 +152,38 @@ def test_long_frames_vs_reference(c):
         assert synth.sha256_tensor(o["v"]) == c["v_sha256"] and synth.sha256_tensor(o["f"]) == c["f_sha256"]
 
 
+STAGE_CHAIN = load_json("stage_chain_cases.json")["cases"]
+
+
+def _chain_id(c):
+    extra = "".join(f"-{k}{c[k]:.4g}" for k in ("ratio", "temp") if c[k] is not None)
+    return f"{c['name']}-{c['F']}x{c['N']}x{c['D']}-{c['dtype']}-{c['dist']}-b{c['base']}{extra}"
+
+
+@pytest.mark.parametrize("mode", ["torch", "exact"])
+@pytest.mark.parametrize("c", STAGE_CHAIN, ids=_chain_id)
+def test_stage_chain_vs_reference(c, mode):
+    """The chain the reference's Qwen2.5-VL / Qwen3-VL hooks call stage by stage (tests/golden/stage_chain_cases.json): in
+    'torch' mode the oracle's chain reproduces every link of the reference's -- channel order, selected features, scores,
+    per-frame uniqueness, scales, budgets, kept indices; half precision bit for bit, fp32 scores within 1e-5 -- and in
+    'exact' mode every link the generator found equal."""
+    from _stage_chain import case_input, check_against_golden, oracle_chain
+    rec = c["oracle"][mode]
+    if mode == "torch":
+        assert all(ok is True for ok in rec.values() if isinstance(ok, bool)), rec
+    O.set_mode(mode)
+    try:
+        x = case_input(c, make_input)
+        assert synth.sha256_tensor(x) == c["x_sha256"], "synthetic generator is not bit-portable"
+        o = oracle_chain(x, c["N"], c["base"], c["ratio"], c["temp"])
+        _, var = O.select_low_var_channel_idx(x)
+    finally:
+        O.set_mode("exact")
+    from _stage_chain import digest
+    assert digest(var) == c["var_sha256"]
+    check_against_golden(o, c, mode, links=None if mode == "torch" else {k for k, ok in rec.items() if ok is True})
+
+
 def test_long_frame_goldens_can_catch_a_missed_replay():
     """The fixture's coverage: the N edges of the kernels' code paths, and fp16 `cancel` frames above 512 tokens --
     simple and tail columns -- where fp64-exact centres differ from the reference's (a pass that skipped or misordered

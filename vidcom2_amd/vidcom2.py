@@ -72,7 +72,11 @@ def _prep(x: torch.Tensor, what: str) -> torch.Tensor:
     require_device(x, what)
     if x.dtype not in DTYPE_CODE:
         raise TypeError(f"{what}: unsupported dtype {x.dtype} (fp32 / bf16 / fp16 only)")
-    return x if x.is_contiguous() else x.contiguous()
+    if not x.is_contiguous():
+        return x.contiguous()
+    # include/vc2.h: base pointers are 16-byte aligned (the sweeps load whole 16-byte vectors).  torch's allocations are;
+    # a view into one (a row slice of an odd-width tensor, a storage offset) need not be: it is copied
+    return x if x.data_ptr() % 16 == 0 else x.clone()
 
 
 @dataclass
