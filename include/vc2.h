@@ -202,6 +202,34 @@ int vc2_compress_ex2(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
                      int64_t* K_host, void* stream);
 int64_t vc2_wait_host_count(const int64_t* K_host, double timeout_s);
 
+/* vc2_compress_ex2 with the method's three hyper-parameters besides the retention ratio.  params == NULL: the reference's
+ * defaults -- vc2_compress_ex2 forwards here with NULL -- and a set EQUAL to them (int(D * 0.5) channels, temp 0.01, the
+ * five scales 2^-3 .. 2^1 in order) is the same pass: the same kernel instantiations, launches and bits.
+ *   channels  C = int(D * ratio) of select_low_var_channels (vidcom2.py:41), computed by the caller the way Python does;
+ *             1 <= C <= min(D, 4096).  C == D takes the two-launch variance + selection form; C != D / 2 takes the
+ *             row-interleaved sweep 2 (the streamlined and torch-ordered forms are built for C = D / 2).
+ *   temp      compute_scales' temp (vidcom2.py:66); finite, > 0
+ *   alphas    _multi_scale_gaussian's scales (vidcom2.py:54, :59-62) in LIST order, the order Python's sum() adds the
+ *             terms; each finite and > 0; 1..16 of them.  Scales other than the reference's five go BY VALUE into sweep
+ *             3's epilogue, which then computes like vc2_multi_scale_gaussian: two_a = float(2.0 * a), the quotient
+ *             correctly rounded, every term rounded to T, v_exp_f32 where it provably rounds like the fp64 exp
+ *             (|arg| <= 16 and not boundary-near), the fp64 exp elsewhere.
+ * channels < 1 or > D, a non-positive or non-finite temp or scale, n_alphas < 1: VC2_ERR_ARG; channels > 4096 or
+ * n_alphas > 16: VC2_ERR_UNSUPPORTED; nothing is enqueued.  The workspace of vc2_workspace_bytes serves every set; every
+ * numerics mode, VC2_FLAG_HAVE_STATS, tail_rows, the host mirror and both mappings work as without params.
+ * The frame-sharded entry points below keep the reference's defaults: a parametrised sharded pass does not exist. */
+typedef struct {
+  int64_t channels;
+  double temp;
+  int32_t n_alphas;
+  double alphas[16];
+} vc2_pass_params;
+int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale,
+                     int map_mode, int64_t grid_h, const void* gather_src, int64_t gather_rows,
+                     void* ws, size_t ws_bytes, void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks,
+                     int64_t* K_out, void* v_T, void* f_T, const void* tail, int64_t tail_rows, int flags,
+                     int64_t* K_host, const vc2_pass_params* params, void* stream);
+
 /* ---- upstream fusion: LLaVA's get_2dPool (llava/model/llava_arch.py:171-190) + sweep 1 -------
  * xin T[F, H*W, D] (the projector output, token-major) -> x_out T[F, h*w, D] = its 2x2 pool, and the sweep-1
  * channel-statistics partials of x_out in ws (workspace of vc2_workspace_bytes(F, h*w, D)): the pooled tensor is

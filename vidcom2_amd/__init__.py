@@ -17,6 +17,7 @@ from .vidcom2 import (  # noqa: F401
     compress,
     compress_batch,
     CompressionResult,
+    PassParams,
 )
 
 __all__ = [

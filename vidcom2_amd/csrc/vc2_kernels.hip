@@ -2890,6 +2890,12 @@ __global__ __launch_bounds__(256) void k_vc_finish(const uint8_t* __restrict__ v
   }
 }
 
+// a caller's Gaussian scales, passed BY VALUE to the kernels that take them (k_multi_scale_gaussian, and k_dist's
+// epilogue for a pass with vc2_pass_params): two_a[i] = float(2.0 * alpha_i) -- python's `2 * a` scalar as the fp32
+// divisor torch makes of it -- in list order
+constexpr int kMaxAlphas = 16;
+struct MsgAlphas { float two_a[kMaxAlphas]; int n; };
+
 // 5-scale Gaussian sum of one squared distance (vidcom2.py:62): every op rounded to T, exp = fp64 exp rounded once
 template <int DT>
 __device__ __forceinline__ float gauss_term(float dist, int a) {
@@ -2926,6 +2932,30 @@ __device__ __forceinline__ float gauss_sum(float dist) {
   }
   return acc;
 }
+
+// The Gaussian sum over a caller's scales (a pass with vc2_pass_params): k_multi_scale_gaussian's arithmetic -- the
+// division correctly rounded (no power-of-two shortcut: the scales are arbitrary), every term rounded to T, 0 + t1 exact,
+// then RN_T(acc + t) in list order -- with gauss_term_fast's v_exp_f32 value where it is proven to round like the fp64
+// exp (|arg| <= 16, not boundary-near) and the fp64 exp elsewhere.  One (row, centre) per thread: the terms are few and
+// the fp64 ones need no second pass over a list.
+template <int DT>
+__device__ __forceinline__ float gauss_sum_table(float dist, const MsgAlphas& al) {
+  float acc = 0.f;
+  for (int a = 0; a < al.n; ++a) {
+    const float arg = rnT<DT>((-dist) / al.two_a[a]);
+    float e = 0.f;
+    bool done = false;
+    if constexpr (DT != VC2_F32) {
+      const float ef = __builtin_amdgcn_exp2f(arg * 1.44269504088896341f);
+      done = fabsf(arg) <= 16.f && !near_T_boundary<DT>(ef, kFragileUlpsExp);
+      e = rnT<DT>(ef);
+    }
+    if (!done) e = rnT<DT>(float(exp(double(arg))));
+    acc = (a == 0) ? e : rnT<DT>(acc + e);                   // Python sum(): 0 + t1 is exact
+  }
+  return acc;
+}
+__device__ __forceinline__ const MsgAlphas& first_alphas(const MsgAlphas& al) { return al; }
 
 // ---- sweep 3 arithmetic ---------------------------------------------------------------------------------------
 // The sweep is bound by VALU ISSUE, not by memory (measured, scripts/ubench/valu_rates.hip: a wave64 shift, cvt_pk,
@@ -3009,7 +3039,9 @@ __host__ __device__ inline int dist_split_cut(int j, int S, int N, int skew_q10)
   return int((num + den / 2) / den);
 }
 
-template <int DT, int VEC, int NPLB, int ACC, int QUAD = 0>
+// AL: empty -- the reference's five scales at compile time (gauss_term / gauss_term_fast) -- or one MsgAlphas: the epilogue
+// takes the caller's table (gauss_sum_table).  The empty pack leaves the default instantiations' parameter list as it was.
+template <int DT, int VEC, int NPLB, int ACC, int QUAD = 0, typename... AL>
 __global__ __launch_bounds__(kRowWaves * 64, 1) void k_dist(const void* __restrict__ x, int N, int D, int CV, int C,
                                                          const int* __restrict__ cols,
                                                          const int* __restrict__ spos, int strict, int S,
@@ -3018,8 +3050,11 @@ __global__ __launch_bounds__(kRowWaves * 64, 1) void k_dist(const void* __restri
                                                          const float* __restrict__ vc,
                                                          const float* __restrict__ fc,
                                                          void* __restrict__ v_T, void* __restrict__ f_T,
-                                                         float* __restrict__ total, double* __restrict__ vpart) {
+                                                         float* __restrict__ total, double* __restrict__ vpart,
+                                                         AL... al) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  static_assert(sizeof...(AL) <= 1, "at most one alpha table");
+  constexpr bool kTable = sizeof...(AL) != 0;
   constexpr int ES = Tr<DT>::ES;
   constexpr bool kFast = ACC == 1 && DT == VC2_BF16;
   const size_t rowb = row_lds_bytes(D, ES);
@@ -3315,6 +3350,12 @@ __global__ __launch_bounds__(kRowWaves * 64, 1) void k_dist(const void* __restri
   }
   // ---- phase 3: Gaussian sums, total, partial frame sum ---------------------------------------------
   VC2_WGTIME(0, 1);
+  if constexpr (kTable) {
+    // a caller's scales: thread t owns (row t / 2, centre t % 2); its sum lands in ebuf[t]
+    const MsgAlphas& tab = first_alphas(al...);
+    for (int t = tid; t < nrows * 2; t += kRowWaves * 64) ebuf[t] = gauss_sum_table<DT>(dists[t], tab);
+    __syncthreads();
+  } else {
   for (int t = tid; t < nrows * 10; t += kRowWaves * 64) {
     const int nl = t / 10, j = t - nl * 10;
     float e;
@@ -3327,13 +3368,16 @@ __global__ __launch_bounds__(kRowWaves * 64, 1) void k_dist(const void* __restri
     ebuf[t] = gauss_term<DT>(dists[2 * nl + (j >= 5 ? 1 : 0)], j >= 5 ? j - 5 : j);
   }
   __syncthreads();
+  }
   if (wave == 0) {
     double vd = 0.0;
     if (lane < nrows) {
-      const float* e = ebuf + lane * 10;
-      float v = e[0], g = e[5];
+      const float* e = ebuf + lane * (kTable ? 2 : 10);
+      float v = e[0], g = e[kTable ? 1 : 5];
+      if constexpr (!kTable) {
 #pragma unroll
       for (int a = 1; a < 5; ++a) { v = rnT<DT>(v + e[a]); g = rnT<DT>(g + e[5 + a]); }
+      }
       const int64_t row = int64_t(f) * N + n0 + lane;
       if (v_T) stT<DT>(v_T, row, v);
       if (f_T) stT<DT>(f_T, row, g);
@@ -3440,8 +3484,6 @@ __global__ __launch_bounds__(kBudNT) void k_scales(const float* __restrict__ s, 
 // row: RN_T(RN_T(x - c)^2) per element, the row sum exact (fp64) or -- `strict` -- in torch's cascade
 // order over the columns as they are stored, then the Gaussian sum over the caller's scales.
 constexpr int kMsgWaves = 4;
-constexpr int kMaxAlphas = 16;
-struct MsgAlphas { float two_a[kMaxAlphas]; int n; };
 
 template <int DT>
 __global__ __launch_bounds__(kMsgWaves * 64) void k_multi_scale_gaussian(const void* __restrict__ x, int64_t R,
@@ -4852,11 +4894,12 @@ int launch_norm_fix_t(const Plan& p, const void* x, const ChanSet& cs, void* ws,
 struct DistOut { void* v_T; void* f_T; float* total; };
 
 template <int DT, int VEC, int NPLB, int ACC>
-int launch_dist_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, const DistOut& o, hipStream_t st) {
+int launch_dist_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, const DistOut& o, hipStream_t st,
+                    const MsgAlphas* al) {
   const int* cols = cs.cols; const int C = cs.C;
   const size_t area = (std::max(size_t(kRowWaves) * row_lds_bytes(int(p.D), Tr<DT>::ES), size_t(C) * 4 + 16) + 15) / 16 * 16;
   const size_t smem = area + size_t(kDistMaxRows) * (4 + 8 + 40 + 8 + 20 + 1) + 64;
-  auto launch = [&](auto kernel) -> int {
+  auto launch = [&](auto kernel, auto... table) -> int {
     int rc = allow_big_lds(kernel, smem, "k_dist");
     if (rc) return rc;
     ProfScope ps_(KID_DIST, st);
@@ -4865,20 +4908,27 @@ int launch_dist_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, c
                        wsp<float>(ws, p.o_den),
                        (DT == VC2_F16 && s2v2_nch(p, cs) == 0) ? (uint8_t*)nullptr : wsp<uint8_t>(ws, p.o_rflag),   // (fp16: only k_norm_colsum2 writes it)
                        wsp<float>(ws, p.o_vc),
-                       wsp<float>(ws, p.o_fc), o.v_T, o.f_T, o.total, wsp<double>(ws, p.o_vpart));
+                       wsp<float>(ws, p.o_fc), o.v_T, o.f_T, o.total, wsp<double>(ws, p.o_vpart), table...);
     return VC2_OK;
   };
+  if (al) {                                                                      // a caller's scales: the table instantiations
+    if constexpr (ACC == 1 && NPLB % 4 == 0) {
+      if (cols && (C & 3) == 0) return launch(k_dist<DT, VEC, NPLB, ACC, 1, MsgAlphas>, *al);
+    }
+    return launch(k_dist<DT, VEC, NPLB, ACC, 0, MsgAlphas>, *al);
+  }
   if constexpr (ACC == 1 && NPLB % 4 == 0) {
     if (cols && (C & 3) == 0) return launch(k_dist<DT, VEC, NPLB, ACC, 1>);      // tables in 16-byte loads
   }
   return launch(k_dist<DT, VEC, NPLB, ACC, 0>);
 }
 template <int DT, int VEC, int NPLB>
-int launch_dist_t(const Plan& p, const void* x, const ChanSet& cs, void* ws, const DistOut& o, hipStream_t st) {
+int launch_dist_t(const Plan& p, const void* x, const ChanSet& cs, void* ws, const DistOut& o, hipStream_t st,
+                  const MsgAlphas* al) {
   if constexpr (DT != VC2_F32) {
-    if (fast_acc(p, cs)) return launch_dist_acc<DT, VEC, NPLB, 1>(p, x, cs, ws, o, st);
+    if (fast_acc(p, cs)) return launch_dist_acc<DT, VEC, NPLB, 1>(p, x, cs, ws, o, st, al);
   }
-  return launch_dist_acc<DT, VEC, NPLB, 0>(p, x, cs, ws, o, st);
+  return launch_dist_acc<DT, VEC, NPLB, 0>(p, x, cs, ws, o, st, al);
 }
 // compact positions per lane -> compile-time bucket (28 = 3584-d, 32 = 4096-d models)
 #define VC2_DISPATCH_NPL(npl, FN, ...)                                   \
@@ -5013,14 +5063,15 @@ int zero_counters(const Plan& p, void* ws, hipStream_t st) {
 
 // sweep 3 incl. the per-token epilogue; s != nullptr: also the per-frame uniqueness scores (stage APIs / sharded
 // path -- the fused pass hands the workgroup partials straight to k_select)
+// al: a caller's Gaussian scales (nullptr: the reference's five, at compile time)
 int launch_phase2(const Plan& p, const void* x, const ChanSet& cs, void* ws, void* v_T, void* f_T,
-                  float* total, float* s, hipStream_t st) {
+                  float* total, float* s, hipStream_t st, const MsgAlphas* al = nullptr) {
   const int C = cs.C;
   if (p.rows_per_split2 > kDistMaxRows) return fail(VC2_ERR_UNSUPPORTED, "internal: sweep-3 split too long");
   { int rc = VC2_OK;
   const int npl = int(cdiv(C, 64));
   const DistOut o{v_T, f_T, total};
-  VC2_DISPATCH_VEC(p, rc = VC2_DISPATCH_NPL(npl, launch_dist_t, p, x, cs, ws, o, st));
+  VC2_DISPATCH_VEC(p, rc = VC2_DISPATCH_NPL(npl, launch_dist_t, p, x, cs, ws, o, st, al));
   if (rc) return rc; }
   if (s) {
     ProfScope ps_(KID_EPILOGUE, st);
@@ -5653,7 +5704,47 @@ int vc2_compress_ex2(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
                      int64_t grid_h, const void* gather_src, int64_t gather_rows, void* ws, size_t ws_bytes,
                      void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
                      const void* tail, int64_t tail_rows, int flags, int64_t* K_host, void* stream) {
+  return vc2_compress_ex3(x, F, N, D, dtype, base_scale, map_mode, grid_h, gather_src, gather_rows, ws, ws_bytes, out_rows,
+                          idx_out, cap, ks, K_out, v_T, f_T, tail, tail_rows, flags, K_host, nullptr, stream);
+}
+
+// the reference's hyper-parameters: int(D * 0.5) channels (vidcom2.py:41), temp 0.01 (:66), alphas 2^-3 .. 2^1 (:54)
+constexpr double kRefTemp = 0.01;
+constexpr double kRefAlphas[5] = {0.125, 0.25, 0.5, 1.0, 2.0};
+
+int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale, int map_mode,
+                     int64_t grid_h, const void* gather_src, int64_t gather_rows, void* ws, size_t ws_bytes,
+                     void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
+                     const void* tail, int64_t tail_rows, int flags, int64_t* K_host, const vc2_pass_params* params,
+                     void* stream) {
   if (!x || !idx_out || !ks || !K_out) return fail(VC2_ERR_ARG, "null pointer");
+  // the pass's hyper-parameters: checked before anything else so that nothing is enqueued on a bad set.  A set equal to the
+  // reference's is the default pass: the same kernel instantiations as params == NULL.
+  int64_t kc = int64_t(double(D) * 0.5);                  // int(x.shape[-1] * ratio), vidcom2.py:41
+  double temp = kRefTemp;
+  MsgAlphas alphas;
+  const MsgAlphas* al = nullptr;
+  if (params) {
+    if (params->channels < 1 || params->channels > D)
+      return fail(VC2_ERR_ARG, "params: %lld channels of %lld", (long long)params->channels, (long long)D);
+    if (!(params->temp > 0.0) || !std::isfinite(params->temp)) return fail(VC2_ERR_ARG, "params: temp must be finite and > 0");
+    if (params->n_alphas < 1) return fail(VC2_ERR_ARG, "params: no Gaussian scales");
+    if (params->n_alphas > kMaxAlphas) return fail(VC2_ERR_UNSUPPORTED, "params: more than %d Gaussian scales", kMaxAlphas);
+    for (int i = 0; i < params->n_alphas; ++i)
+      if (!(params->alphas[i] > 0.0) || !std::isfinite(params->alphas[i]))
+        return fail(VC2_ERR_ARG, "params: Gaussian scale %d must be finite and > 0", i);
+    if (params->channels > 4096) return fail(VC2_ERR_UNSUPPORTED, "params: more than 4096 scored channels");
+    kc = params->channels;
+    temp = params->temp;
+    bool ref_scales = params->n_alphas == 5;
+    for (int i = 0; ref_scales && i < 5; ++i) ref_scales = params->alphas[i] == kRefAlphas[i];
+    if (!ref_scales) {
+      alphas.n = params->n_alphas;
+      for (int i = 0; i < kMaxAlphas; ++i)                 // python: -d / (2 * a), scalar -> fp32
+        alphas.two_a[i] = i < params->n_alphas ? float(2.0 * params->alphas[i]) : 1.0f;
+      al = &alphas;
+    }
+  }
   if (tail_rows < 0 || (tail_rows > 0 && !tail)) return fail(VC2_ERR_ARG, "tail_rows without tail");
   if (N > 8192) return fail(VC2_ERR_UNSUPPORTED, "N=%lld > 8192 tokens per frame", (long long)N);
   if (map_mode == VC2_MAP_GRID_VID && (grid_h <= 0 || grid_h * grid_h != N))
@@ -5680,7 +5771,6 @@ int vc2_compress_ex2(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   }
   float* var_f32 = wsp<float>(ws, p.o_var_f32);
   int* cols = wsp<int>(ws, p.o_cols);
-  const int64_t kc = int64_t(double(D) * 0.5);            // int(x.shape[-1] * ratio), vidcom2.py:41
   const bool strict = cur_mode() && p.ES == 2;
   int* spos = strict ? wsp<int>(ws, p.o_spos) : nullptr;
   int* perm = strict ? wsp<int>(ws, p.o_perm) : nullptr;
@@ -5735,16 +5825,16 @@ int vc2_compress_ex2(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   // kernel boundaries).  Fusing them into sweep 3's last workgroup through an agent-scope ticket measured SLOWER than
   // a separate kernel -- the release fences write back L2.
   float* s = fused_budget ? nullptr : wsp<float>(ws, p.o_s);
-  if ((rc = launch_phase2(p, x, cs, ws, v_T, f_T, total, s, st))) return rc;
+  if ((rc = launch_phase2(p, x, cs, ws, v_T, f_T, total, s, st, al))) return rc;
   if (fused_budget) {
     rc = launch_select(dtype, total, F, 0, F, N, map_mode, grid_h, ks, wsp<int64_t>(ws, p.o_offs), idx_out, cap, K_out,
-                       BudgetSrc{nullptr, wsp<double>(ws, p.o_vpart), p.S2, nullptr, bs, 0.01, scales, 0,
+                       BudgetSrc{nullptr, wsp<double>(ws, p.o_vpart), p.S2, nullptr, bs, temp, scales, 0,
                                  wsp<int>(ws, p.o_ticket) + kTkStatus, reinterpret_cast<long long*>(K_host),
                                  wsp<int>(ws, p.o_ticket) + kTkSelArrive}, st);
   } else {
-    if ((rc = launch_scales(dtype, s, F, bs, 0.01, wsp<float>(ws, p.o_zbuf), scales, nullptr, st))) return rc;
+    if ((rc = launch_scales(dtype, s, F, bs, temp, wsp<float>(ws, p.o_zbuf), scales, nullptr, st))) return rc;
     rc = launch_select(dtype, total, F, 0, F, N, map_mode, grid_h, ks, wsp<int64_t>(ws, p.o_offs), idx_out, cap, K_out,
-                       BudgetSrc{scales, nullptr, 0, nullptr, bs, 0.01, nullptr, 0, wsp<int>(ws, p.o_ticket) + kTkStatus,
+                       BudgetSrc{scales, nullptr, 0, nullptr, bs, temp, nullptr, 0, wsp<int>(ws, p.o_ticket) + kTkStatus,
                                  reinterpret_cast<long long*>(K_host), wsp<int>(ws, p.o_ticket) + kTkSelArrive}, st);
   }
   if (rc) return rc;

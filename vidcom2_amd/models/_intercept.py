@@ -56,6 +56,54 @@ def retention_ratio() -> float:
     return float(os.getenv("R_RATIO", "0.25"))
 
 
+def _float_knob(name: str):
+    raw = os.getenv(name)
+    if raw is None:
+        return None
+    try:
+        return float(raw)
+    except ValueError:
+        raise ValueError(f"{name}={raw!r}: expected a number") from None
+
+
+def pass_params():
+    """`VC2_CHANNEL_RATIO` (float), `VC2_TEMP` (float) and `VC2_ALPHAS` (comma-separated floats), read at call time: the
+    hyper-parameters the reference fixes in its stage functions' defaults (vidcom2.py:38, :54, :64), as the `PassParams`
+    the hooks hand to `compress` / `compress_batch`.  None when none of them is set -- the hooks' call is then the one
+    without params; an unset knob keeps the reference's value.  A malformed or out-of-range value raises ValueError
+    naming the knob."""
+    from ..vidcom2 import PassParams
+    ratio, temp, raw = _float_knob("VC2_CHANNEL_RATIO"), _float_knob("VC2_TEMP"), os.getenv("VC2_ALPHAS")
+    if ratio is None and temp is None and raw is None:
+        return None
+    kw = {}
+    if raw is not None:
+        try:
+            kw["alphas"] = tuple(float(a) for a in raw.split(","))
+        except ValueError:
+            raise ValueError(f"VC2_ALPHAS={raw!r}: expected comma-separated numbers") from None
+    if ratio is not None:
+        kw["channel_ratio"] = ratio
+    if temp is not None:
+        kw["temp"] = temp
+    for knob, key in (("VC2_CHANNEL_RATIO", "channel_ratio"), ("VC2_TEMP", "temp"), ("VC2_ALPHAS", "alphas")):
+        if key in kw:                                    # each knob checked on its own, so that the error can name it
+            try:
+                PassParams(**{key: kw[key]})
+            except ValueError as e:
+                raise ValueError(f"{knob}={os.getenv(knob)!r}: {e}") from None
+            except NotImplementedError as e:
+                raise NotImplementedError(f"{knob}={os.getenv(knob)!r}: {e}") from None
+    return PassParams(**kw)
+
+
+def params_kwargs() -> dict:
+    """`{"params": pass_params()}` for the hooks' calls into the pass; empty when no knob is set, so that the call is
+    exactly the one without params."""
+    p = pass_params()
+    return {} if p is None else {"params": p}
+
+
 def compressor_enabled() -> bool:
     """`COMPRESSOR=vidcom2` env knob (models/qwen2_5_vl.py:121)."""
     return os.getenv("COMPRESSOR") == "vidcom2"

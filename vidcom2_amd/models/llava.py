@@ -27,7 +27,7 @@ import torch
 
 from ..autograd import attach_pool, wants_grad
 from ..vidcom2 import vidcom2_compression
-from ._intercept import original_method, retention_ratio, shadow
+from ._intercept import original_method, params_kwargs, retention_ratio, shadow
 
 __all__ = ["cus_prepare_inputs_labels_for_multimodal"]
 
@@ -70,14 +70,19 @@ class _CompressOnFlatten(torch.Tensor):
                 # kept rows + the newline row behind them in ONE gather launch
                 from ..vidcom2 import MODEL_SPECS, compress
                 res = compress(flat, MODEL_SPECS["llava_ov"]["tpf"], retention_ratio(), tail=newline[None],
-                               stats_ws=getattr(self, "_vc2_stats_ws", None))
+                               stats_ws=getattr(self, "_vc2_stats_ws", None), **params_kwargs())
                 rows = res.rows[: res.K].as_subclass(_NewlineFused)
                 rows._vc2_fused = (res.rows, newline.data_ptr())
                 return rows
             ws = getattr(self, "_vc2_stats_ws", None)
             if ws is not None and flat.is_cuda:
                 from ..vidcom2 import MODEL_SPECS, compress
-                return compress(flat, MODEL_SPECS["llava_ov"]["tpf"], retention_ratio(), stats_ws=ws).rows
+                return compress(flat, MODEL_SPECS["llava_ov"]["tpf"], retention_ratio(), stats_ws=ws,
+                                **params_kwargs()).rows
+            pk = params_kwargs()
+            if pk:                        # (vidcom2_compression keeps the reference's signature: the pass itself)
+                from ..vidcom2 import MODEL_SPECS, compress
+                return compress(flat, MODEL_SPECS["llava_ov"]["tpf"], retention_ratio(), **pk).rows
             return vidcom2_compression(flat, base_scale=retention_ratio())
         return flat
 
@@ -151,7 +156,12 @@ def cus_prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, atte
                     from ..vidcom2 import MODEL_SPECS, compress
                     spec = MODEL_SPECS["llava_vid"]
                     return compress(flat, spec["tpf"], retention_ratio(), "grid_vid", spec["grid"], out,
-                                    stats_ws=ws).rows
+                                    stats_ws=ws, **params_kwargs()).rows
+                pk = params_kwargs()
+                if pk:                    # (vidcom2_compression keeps the reference's signature: the pass itself)
+                    from ..vidcom2 import MODEL_SPECS, compress
+                    spec = MODEL_SPECS["llava_vid"]
+                    return compress(flat, spec["tpf"], retention_ratio(), "grid_vid", spec["grid"], out, **pk).rows
                 return vidcom2_compression(flat, "llava_vid", base_scale=retention_ratio(), img_feat=out)
 
             patches["add_token_per_grid"] = add_token_per_grid

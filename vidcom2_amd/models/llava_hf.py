@@ -37,7 +37,8 @@ import torch
 
 from ..autograd import attach_pool, wants_grad
 from ..vidcom2 import compress, compress_batch
-from ._intercept import batched_prefill_enabled, compressor_enabled, original_method, retention_ratio, shadow
+from ._intercept import (batched_prefill_enabled, compressor_enabled, original_method, params_kwargs, retention_ratio,
+                         shadow)
 from ._prefill_prune import _DecodeLayout, _gather_slots, decode_state, run_decode_step, run_with_pruning
 from .qwen2_5_vl import _cache_is_empty
 
@@ -50,12 +51,12 @@ _POOL_LOGGED = [False]
 
 def _keep_indices(x: torch.Tensor, n: int, base_scale: float, stats_ws=None) -> torch.Tensor:
     """Kept token indices (ascending, int64) of one video's `[F*n, D]` tokens."""
-    return compress(x, n, base_scale, "linear", gather=False, stats_ws=stats_ws).global_idx
+    return compress(x, n, base_scale, "linear", gather=False, stats_ws=stats_ws, **params_kwargs()).global_idx
 
 
 def _keep_indices_many(xs, n: int, base_scale: float):
     """`_keep_indices` of every row's video, all of them in flight (one host synchronisation for every count)."""
-    return [r.global_idx for r in compress_batch(list(xs), n, base_scale, gather=False)]
+    return [r.global_idx for r in compress_batch(list(xs), n, base_scale, gather=False, **params_kwargs())]
 
 
 def fused_pool_enabled() -> bool:

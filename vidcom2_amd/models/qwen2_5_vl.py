@@ -28,7 +28,7 @@ import torch
 from torch import Tensor
 
 from ..vidcom2 import compress, compress_batch
-from ._intercept import compressor_enabled, original_method, retention_ratio
+from ._intercept import compressor_enabled, original_method, params_kwargs, retention_ratio
 from ._prefill_prune import decode_state, run_decode_step, run_with_pruning
 
 __all__ = ["Qwen2_5_VLModel_forward", "_compute_keep_indices", "_compute_keep_indices_many"]
@@ -42,7 +42,7 @@ def _compute_keep_indices(flat_features: Tensor, grid_thw: Tensor, spatial_merge
     frame_tokens = (h * w) // (spatial_merge_size ** 2)
     if frame_tokens <= 0 or flat_features.numel() == 0:
         return torch.arange(flat_features.shape[0], device=flat_features.device)
-    return compress(flat_features, frame_tokens, base_scale, "linear", gather=False).global_idx
+    return compress(flat_features, frame_tokens, base_scale, "linear", gather=False, **params_kwargs()).global_idx
 
 
 def _compute_keep_indices_many(feats, grids, spatial_merge_size: int, base_scale: float) -> Tensor:
@@ -62,7 +62,8 @@ def _compute_keep_indices_many(feats, grids, spatial_merge_size: int, base_scale
             jobs.append((i, frame_tokens))
         offset += f.shape[0]
     if jobs:
-        res = compress_batch([feats[i] for i, _ in jobs], [n for _, n in jobs], base_scale, gather=False)
+        res = compress_batch([feats[i] for i, _ in jobs], [n for _, n in jobs], base_scale, gather=False,
+                             **params_kwargs())
         for (i, _), r in zip(jobs, res):
             kept[i] = r.global_idx
     if not kept:

@@ -32,7 +32,7 @@ import torch
 from torch import Tensor
 
 from ..vidcom2 import _as_int, compress
-from ._intercept import original_method, retention_ratio, shadow
+from ._intercept import original_method, params_kwargs, retention_ratio, shadow
 from ._prefill_prune import PruneState, _prune_attention, run_with_pruning
 
 __all__ = ["Qwen2VL_ViT_forward", "Qwen2VLGeneration_forward", "Qwen2VLModel_forward", "_keep_index"]
@@ -44,7 +44,7 @@ def _keep_index(merged: Tensor, grid_thw: Tensor, merge_size: int = 2) -> Tensor
     call is an error."""
     token_per_frame = (grid_thw[:, 1] // merge_size) * (grid_thw[:, 2] // merge_size)
     tpf = _as_int(token_per_frame)
-    return compress(merged, tpf, retention_ratio(), "linear", gather=False).global_idx
+    return compress(merged, tpf, retention_ratio(), "linear", gather=False, **params_kwargs()).global_idx
 
 
 def _merged_of(out):

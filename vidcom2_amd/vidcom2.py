@@ -14,6 +14,7 @@ from __future__ import annotations
 import atexit
 import collections
 import ctypes
+import math
 import os
 import threading
 import time
@@ -38,6 +39,100 @@ MODEL_SPECS: Dict[str, Dict[str, Any]] = {
 }
 _DYNAMIC_TPF = {"qwen2_vl", "qwen2_5_vl", "qwen3_vl"}
 _ALPHAS = [2 ** k for k in range(-3, 2)]          # vidcom2.py:54
+
+
+_MAX_ALPHAS = 16                                   # include/vc2.h: vc2_pass_params.alphas
+_MAX_CHANNELS = 4096                               # scored channels the sweeps cover (64 compact positions per lane)
+
+
+class _CPassParams(ctypes.Structure):
+    """include/vc2.h: vc2_pass_params."""
+    _fields_ = [("channels", ctypes.c_int64), ("temp", ctypes.c_double), ("n_alphas", ctypes.c_int32),
+                ("alphas", ctypes.c_double * _MAX_ALPHAS)]
+
+
+class PassParams:
+    """The method's three hyper-parameters besides the retention ratio, for the one-launch pass (`compress`,
+    `compress_batch`, `CompressPlan`): the share of low-variance channels that are scored (`select_low_var_channels`'
+    ratio, vidcom2.py:38), the temperature of the budget softmax (`compute_scales`' temp, vidcom2.py:64) and the
+    Gaussian scales (vidcom2.py:54) in the order Python's `sum()` adds their terms.  Immutable and hashable; validated
+    here, on the host.  An instance equal to the reference's defaults is the default pass (`is_default`): it shares
+    kernels, bits and cached plans with a call without params."""
+    __slots__ = ("channel_ratio", "temp", "alphas")
+
+    def __init__(self, channel_ratio: float = 0.5, temp: float = 0.01, alphas=(0.125, 0.25, 0.5, 1.0, 2.0)):
+        try:
+            ratio, t, al = float(channel_ratio), float(temp), tuple(float(a) for a in alphas)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"PassParams: {e}") from None
+        if not (0.0 < ratio <= 1.0):                     # (NaN fails the comparison too)
+            raise ValueError(f"PassParams: channel_ratio {channel_ratio!r} outside (0, 1]")
+        if not (t > 0.0 and math.isfinite(t)):
+            raise ValueError(f"PassParams: temp {temp!r} must be finite and > 0")
+        if not al:
+            raise ValueError("PassParams: alphas is empty")
+        if any(not (a > 0.0 and math.isfinite(a)) for a in al):
+            raise ValueError(f"PassParams: every alpha must be finite and > 0, got {list(alphas)!r}")
+        if len(al) > _MAX_ALPHAS:
+            raise NotImplementedError(f"PassParams: {len(al)} Gaussian scales; the pass takes at most {_MAX_ALPHAS}")
+        object.__setattr__(self, "channel_ratio", ratio)
+        object.__setattr__(self, "temp", t)
+        object.__setattr__(self, "alphas", al)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("PassParams is immutable")
+
+    def __delattr__(self, name):
+        raise AttributeError("PassParams is immutable")
+
+    def _key(self):
+        return (self.channel_ratio, self.temp, self.alphas)
+
+    def __eq__(self, other):
+        return isinstance(other, PassParams) and self._key() == other._key()
+
+    def __hash__(self):
+        return hash(self._key())
+
+    def __repr__(self):
+        return f"PassParams(channel_ratio={self.channel_ratio!r}, temp={self.temp!r}, alphas={self.alphas!r})"
+
+    def __reduce__(self):
+        return (PassParams, self._key())
+
+    def channels(self, D: int) -> int:
+        """int(D * ratio): the number of channels the reference scores (vidcom2.py:41)."""
+        return int(int(D) * self.channel_ratio)
+
+    @property
+    def is_default(self) -> bool:
+        return self._key() == _DEFAULT_PARAMS_KEY
+
+
+_DEFAULT_PARAMS_KEY = (0.5, 0.01, tuple(float(a) for a in _ALPHAS))
+
+
+def _norm_params(params: Optional["PassParams"]) -> Optional["PassParams"]:
+    """None for the reference's defaults ("no params": the plain call, its kernels and its cached plans)."""
+    if params is None:
+        return None
+    if not isinstance(params, PassParams):
+        raise TypeError(f"params must be a PassParams, got {type(params).__name__}")
+    return None if params.is_default else params
+
+
+def _c_params(params: Optional["PassParams"], D: int) -> Optional[_CPassParams]:
+    """vc2_pass_params of a normalised PassParams for rows of D channels; the C ABI's own limits, raised before anything
+    is allocated."""
+    if params is None:
+        return None
+    C = params.channels(D)
+    if C < 1:
+        raise ValueError(f"channel_ratio {params.channel_ratio} selects no channel of {D} (int({D} * ratio) == 0)")
+    if C > _MAX_CHANNELS:
+        raise NotImplementedError(f"channel_ratio {params.channel_ratio} selects {C} of {D} channels; the pass scores at "
+                                  f"most {_MAX_CHANNELS}")
+    return _CPassParams(C, params.temp, len(params.alphas), (ctypes.c_double * _MAX_ALPHAS)(*params.alphas))
 
 
 def _first_tensor(a):
@@ -140,10 +235,12 @@ class CompressPlan:
 
     def __init__(self, F: int, N: int, D: int, dtype, device, base_scale: float = 0.25,
                  mapper: str = "linear", grid_h: int = 0, want_scores: bool = False, gather: bool = True,
-                 tail_rows: int = 0, ws: Optional[torch.Tensor] = None):
+                 tail_rows: int = 0, ws: Optional[torch.Tensor] = None, params: Optional[PassParams] = None):
         if mapper not in ("linear", "grid_vid"):
             raise ValueError(f"unknown mapper {mapper!r}")
         self.F, self.N, self.D, self.dtype, self.device = int(F), int(N), int(D), dtype, torch.device(device)
+        self.params = _norm_params(params)               # None: the reference's hyper-parameters
+        self._cparams = _c_params(self.params, self.D)
         self.base_scale = float(base_scale)
         self.map_mode = MAP_LINEAR if mapper == "linear" else MAP_GRID_VID
         self.grid_h = int(grid_h)
@@ -253,12 +350,14 @@ class CompressPlan:
             khost = kh.addr
         self._armed = st if mirror else None
         with on_device(self.device):
-            rc = lib().vc2_compress_ex2(ptr(flat), self.F, self.N, self.D, DTYPE_CODE[self.dtype], self.base_scale,
+            rc = lib().vc2_compress_ex3(ptr(flat), self.F, self.N, self.D, DTYPE_CODE[self.dtype], self.base_scale,
                                         self.map_mode, self.grid_h, ptr(src if o.rows is not None else None),
                                         src.shape[0], ptr(self.ws), self.ws.numel(), ptr(o.rows), ptr(o.idx),
                                         self.cap, ptr(o.ks), ptr(o.kout), ptr(o.v), ptr(o.f),
                                         ptr(tail if self.tail_rows else None), self.tail_rows,
-                                        1 if have_stats else 0, khost, ctypes.c_void_p(st.cuda_stream))
+                                        1 if have_stats else 0, khost,
+                                        None if self._cparams is None else ctypes.addressof(self._cparams),
+                                        ctypes.c_void_p(st.cuda_stream))
         if rc != 0 and mirror:                           # (nothing was launched: the mirror block is not in flight)
             self._khost.in_flight = False
             self._armed = None
@@ -347,12 +446,13 @@ _PREALLOC = os.environ.get("VC2_PREALLOC", "1") != "0"             # next call's
 
 
 def _cached_plan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores, gather, tail_rows,
-                 fresh_outputs: bool = False) -> "CompressPlan":
+                 fresh_outputs: bool = False, params: Optional[PassParams] = None) -> "CompressPlan":
     device = torch.device(device)
+    params = _norm_params(params)
     if device.index is None:
         device = torch.device(device.type, torch.cuda.current_device())
     key = (F, N, D, dtype, device, float(base_scale), mapper, int(grid_h), bool(want_scores), bool(gather),
-           int(tail_rows), torch.cuda.current_stream(device).cuda_stream, threading.get_ident(), _ffi.get_mode())
+           int(tail_rows), torch.cuda.current_stream(device).cuda_stream, threading.get_ident(), _ffi.get_mode(), params)
     # (the key holds the thread id, so a plan is only ever USED by one thread; the dictionary itself is shared: another
     #  thread's eviction between get and move_to_end raised KeyError before the lock)
     with _PLAN_LOCK:
@@ -360,7 +460,8 @@ def _cached_plan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores
         if plan is not None:
             _PLAN_CACHE.move_to_end(key)
     if plan is None:
-        plan = CompressPlan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores, gather, tail_rows)
+        plan = CompressPlan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores, gather, tail_rows,
+                            params=params)
         if _PLAN_CACHE_MAX > 0:
             with _PLAN_LOCK:
                 _PLAN_CACHE[key] = plan
@@ -470,22 +571,27 @@ def _raise_status(status: int, cap: int, K: int) -> None:
 def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, mapper: str = "linear",
              grid_h: int = 0, img_feat: Optional[torch.Tensor] = None, want_scores: bool = False,
              gather: bool = True, tail: Optional[torch.Tensor] = None,
-             stats_ws: Optional[torch.Tensor] = None) -> CompressionResult:
+             stats_ws: Optional[torch.Tensor] = None, params: Optional[PassParams] = None) -> CompressionResult:
     """One whole pass: feature tensor resident in HBM -> kept rows + indices + budgets.
+    params: channel ratio, softmax temperature and Gaussian scales other than the reference's (PassParams); None, or a
+    PassParams equal to the defaults: the reference's.
     tail ([m, D], e.g. LLaVA's newline embedding): written behind the kept rows by the gather launch itself;
     `rows` is then [K + m, D].  stats_ws: the workspace `fused.pool_stats` returned together with THIS tensor --
     the pass then skips its first sweep.
     Autograd: `rows` is differentiable (vidcom2_amd/autograd.py) with respect to the gathered-from tensor
     (`flattened_feat`, or `img_feat` for grid_vid -- flattened_feat then gets none, as in the reference) and `tail`;
     indices, budgets and scores are not."""
+    params = _norm_params(params)
     x = _prep(flattened_feat, "flattened_feat")
     if x.dim() != 2:
         raise RuntimeError(f"flattened_feat must be 2-D [frames*tokens, dim], got {tuple(x.shape)}")
     R, D = x.shape
     tpf = int(tpf)
+    _c_params(params, D)                  # (the limits of the channel count, before the shape's own errors)
     if tpf <= 0 or R % tpf != 0:
         # the reference fails in frames = x.view(-1, tpf, C) (vidcom2.py:47)
-        raise RuntimeError(f"shape '[-1, {tpf}, {int(D * 0.5)}]' is invalid for input of size {R * int(D * 0.5)}")
+        C = int(D * 0.5) if params is None else params.channels(D)
+        raise RuntimeError(f"shape '[-1, {tpf}, {C}]' is invalid for input of size {R * C}")
     src = None
     if mapper == "grid_vid":
         if img_feat is None:
@@ -509,10 +615,10 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     ntail = 0 if tail is None else tail.shape[0]
     if stats_ws is not None:          # (the statistics live in the caller's workspace: a plan around it, not cached)
         plan = CompressPlan(R // tpf, tpf, D, x.dtype, x.device, base_scale, mapper, grid_h, want_scores, gather,
-                            tail_rows=ntail, ws=stats_ws)
+                            tail_rows=ntail, ws=stats_ws, params=params)
     else:
         plan = _cached_plan(R // tpf, tpf, D, x.dtype, x.device, base_scale, mapper, grid_h, want_scores, gather, ntail,
-                            fresh_outputs=True)
+                            fresh_outputs=True, params=params)
     plan.enqueue(x, src, tail, have_stats=stats_ws is not None, mirror=_EARLY_COUNT)
     if stats_ws is None and _PREALLOC and _PLAN_CACHE_MAX > 0 and plan.output_bytes() <= _SPARE_MAX_BYTES:
         plan.prepare_spare()              # (the GPU is busy for the next ~190 us: the next call's outputs cost nothing here)
@@ -542,22 +648,24 @@ BATCH_LANES = 3          # compress_batch's default: clips in flight (16 cfg5 cl
 
 
 def compress_batch(clips, tpf: int, base_scale: float = 0.25, in_flight: int = BATCH_LANES, gather: bool = True,
-                   own_storage: bool = False):
+                   own_storage: bool = False, params: Optional[PassParams] = None):
     """Compress several clips (a list of [F_i * tpf, D] tensors) with up to `in_flight` of them running
     concurrently, one HIP stream each.  A single pass leaves the GPU idle during its single-workgroup selection
     replays; further clips in flight fill those gaps (DESIGN.md "clips in flight"; every lane keeps a plan = a workspace).
     Returns one CompressionResult per clip, in order.  The reference has no batched form: its harness loops
     over clips (lmms-eval, batch size 1 per rank).
     `tpf` may also be a sequence of one tokens-per-frame value per clip (videos of different grids).
+    params: one PassParams for every clip of the batch (None: the reference's hyper-parameters).
     Storage: for clips of ONE shape every result is a VIEW into batch-wide buffers (one allocation per output kind), so
     keeping any clip's rows / indices alive keeps the whole batch's buffers alive (n * capacity * D elements);
     own_storage=True hands every clip its own tensors instead (one extra device copy of the kept rows).
     Autograd: every clip's rows are differentiable with respect to that clip (vidcom2_amd/autograd.py)."""
     clips = list(clips)
+    params = _norm_params(params)
     if _ag.wants_grad(*clips):
-        return [_attach_clip(r, c) for r, c in zip(_compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage),
-                                                   clips)]
-    return _compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage)
+        return [_attach_clip(r, c) for r, c in zip(_compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage,
+                                                                   params), clips)]
+    return _compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage, params)
 
 
 def _attach_clip(res: CompressionResult, clip: torch.Tensor) -> CompressionResult:
@@ -566,7 +674,8 @@ def _attach_clip(res: CompressionResult, clip: torch.Tensor) -> CompressionResul
     return res
 
 
-def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool, own_storage: bool):
+def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool, own_storage: bool,
+                    params: Optional[PassParams] = None):
     clips = [_prep(c, "clip") for c in clips]
     if not clips:
         return []
@@ -580,6 +689,7 @@ def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool,
     for i, (x, t) in enumerate(zip(clips, tpfs)):
         if x.dim() != 2 or t <= 0 or x.shape[0] % t != 0:
             raise RuntimeError(f"clip {i}: shape {tuple(x.shape)} is not [frames * {t}, dim]")
+        _c_params(params, x.shape[1])      # (the channel count's limits, before anything is enqueued for any clip)
     cur = torch.cuda.current_stream(dev)
     lanes = [cur] + _lane_streams(dev, max(1, min(int(in_flight), len(clips))) - 1)
     plans = {}
@@ -589,7 +699,7 @@ def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool,
         if key not in plans:
             with torch.cuda.stream(lanes[j]):
                 plans[key] = _cached_plan(x.shape[0] // t, t, x.shape[1], x.dtype, dev, base_scale, "linear", 0, False,
-                                          gather, 0)
+                                          gather, 0, params=params)
         return plans[key]
 
     # Clips of one shape (the batched-eval case, BASELINE config 5): ONE allocation per output kind for the whole batch --
