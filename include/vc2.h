@@ -335,16 +335,16 @@ int vc2_cols_grad(const void* g, int64_t R, int64_t C, int64_t D, int dtype, con
  * A rank holds frames [f0, f0+F_local) of a video with F_total frames.  Between the local sweeps the Python
  * layer all-gathers three small fp64 / fp32 arrays over RCCL.  Exchanges 1 and 2 carry CANONICAL partials -- per
  * stat block of 8 frames (mean, M2), per group of 16 frames the sums of the normalised tokens -- that every rank then
- * folds in the same fixed order, so the reduced bits do not depend on the world size (ranks holding a multiple of 16
- * frames; otherwise equal up to fp64 rounding):
+ * folds in the same fixed order, so the reduced bits do not depend on the world size or on how the frames are split
+ * (ranks holding a multiple of 16 frames each, equal or not; otherwise equal up to fp64 rounding):
  *   1. per stat block (mean, M2)   bstats[nb][2][D], nb = F_local / block_frames     -> vc2_chan_var_from_stats
  *   2. per 16-frame group: sums of x^, then bounds of sum |x^|   csum_parts[2 * ceil(F_local/16)][C]   -> vc2_scores_phase2
  *      (the bounds size the video centre's replay margin soundly, see mean_delta in the kernels)
  *   3. per-frame uniqueness   s[F_local]                                               -> vc2_select_sharded
  * F_total (the WHOLE video's frame count) fixes how frames are cut into row groups / splits on every rank. */
 int vc2_stat_block_frames(void);     /* 8: the unsharded pass's stat block */
-/* block_frames: frames per stat block, 1..8; use 8 when F_local is a multiple of 8 (bit-identical to the unsharded
- * pass), else the largest power of two dividing F_local -- the same value on every rank. */
+/* block_frames: frames per stat block, 1..8; use 8 when every rank's F_local is a multiple of 8 (bit-identical to the
+ * unsharded pass), else the largest power of two dividing every rank's F_local -- the same value on every rank. */
 int vc2_chan_stats(const void* x, int64_t F, int64_t N, int64_t D, int dtype, int64_t F_total, int block_frames,
                    void* ws, size_t ws_bytes, double* bstats /*[F / block_frames][2][D]*/, void* stream);
 /* bstats of ALL ranks concatenated in rank order; rows_per_block = block_frames * N (the last block holds the
@@ -365,7 +365,7 @@ int vc2_scores_phase2(const void* x, int64_t F, int64_t N, int64_t D, int dtype,
                       int64_t csum_stride, int64_t rows_per_rank, int64_t R_total, void* ws, size_t ws_bytes, void* v_T,
                       void* f_T, float* total_f32, float* s_f32, void* stream);
 /* Video-centre replay of the frame-sharded pass ("torch order" mode, 16-bit inputs, every rank the same number of
- * rows and at least B of them, B = 16 rows up to 2^19 tokens per video, 32 up to 2^23, 64 up to 2^25 -- torch's
+ * rows -- ranks with unequal row counts: the _ragged forms below -- and at least B of them, B = 16 rows up to 2^19 tokens per video, 32 up to 2^23, 64 up to 2^25 -- torch's
  * level_power 4 / 5 / 6).  Between exchange 2 and phase 2:
  *   vc2_video_centre_blocks  flags the boundary-near video-centre columns (identically on every rank) and writes, for
  *                            the first `cap` of them, a record of 129 + F*N/16 floats to blocks_out[cap][129 + F*N/16]:
@@ -396,7 +396,7 @@ int vc2_scores_phase2_blocks(const void* x, int64_t F, int64_t N, int64_t D, int
  *                                                         video centre in the workspace is corrected in place  (r >= 0)
  * and finally vc2_scores_phase2_blocks(blocks_all = NULL, world = -1): "the centre is final", sweep 3 only.
  * A level-0 block may meet any number of ranks (ranks with fewer rows than a block included); the ranks must hold
- * equal row counts. */
+ * equal row counts (unequal ones: the _ragged forms below). */
 int vc2_video_centre_blocks_round(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
                                   int64_t C, const int32_t* spos, int64_t R_total, int64_t row0, void* ws,
                                   size_t ws_bytes, float* blocks_out, int cap, int col_offset, void* stream);
@@ -405,6 +405,43 @@ int vc2_video_centre_flagged(int64_t F, int64_t N, int64_t D, int dtype, int64_t
 int vc2_video_centre_finish_round(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
                                   int64_t R_total, void* ws, size_t ws_bytes, const float* blocks_all, int world,
                                   int cap, int col_offset, void* stream);
+
+/* Exchange 2b for ranks with UNEQUAL row counts.  The _ragged forms take the layout of the video over the ranks instead of
+ * assuming R_total == world * F * N: `world`, this rank's `rank`, and the HOST array rank_rows[world] (rows = frames * N of
+ * every rank in rank order; their sum is R_total, every entry >= N -- no empty rank --, rank_rows[rank] == F * N).  From it
+ * they take this rank's row0 (the prefix sum) and ONE record stride for all ranks, 129 + max(rank_rows) / 16 floats, so
+ * that the all-gather stays rectangular: blocks_out[cap][stride], blocks_all[world][cap][stride].  A record's layout, the
+ * flags, the rounds and the arithmetic are those of the equal-rank forms (a straddling block is its rows' raw values added
+ * in row order, from however many ranks it meets; complete blocks come from the records); the owner of a video row is
+ * found in the prefix sums of rank_rows, which reach the kernel by value (no copy, no synchronisation).  At most
+ * VC2_RAGGED_MAX_WORLD ranks; more give VC2_ERR_UNSUPPORTED.  The other sharded entry points need no ragged form:
+ * they take (f0, F, F_total) or block counts as they are.  What the caller lays out (vidcom2_amd/sharded.py does):
+ *   exchange 1  block_frames = the largest power of two <= 8 dividing EVERY rank's frame count, the ranks' blocks
+ *               compacted to bstats[sum nb_p][2][D] in rank order -- one uniform grid of the video
+ *   exchange 2  a rank with fewer 16-frame groups than the largest pads INSIDE each half of its csum_parts block (zero
+ *               sums, zero bounds: rows_per_rank = 2 * the largest group count); zeros change neither sums nor bounds
+ * vc2_scores_phase2_blocks_ragged always finishes the cascade (blocks_all must be the gathered records); "the centre is
+ * final" (world = -1) and "no records" stay with vc2_scores_phase2_blocks, which does not look at the layout then. */
+#define VC2_RAGGED_MAX_WORLD 64
+int vc2_video_centre_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                   int64_t C, const int32_t* spos, const double* csum_all, int64_t P,
+                                   int64_t csum_stride, int64_t rows_per_rank, int64_t R_total,
+                                   const int64_t* rank_rows /* host [world] */, int world, int rank, void* ws,
+                                   size_t ws_bytes, float* blocks_out, int cap, void* stream);
+int vc2_video_centre_blocks_round_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                         int64_t C, const int32_t* spos, int64_t R_total,
+                                         const int64_t* rank_rows /* host [world] */, int world, int rank, void* ws,
+                                         size_t ws_bytes, float* blocks_out, int cap, int col_offset, void* stream);
+int vc2_video_centre_finish_round_ragged(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
+                                         int64_t R_total, const int64_t* rank_rows /* host [world] */, int world,
+                                         int rank, void* ws, size_t ws_bytes, const float* blocks_all, int cap,
+                                         int col_offset, void* stream);
+int vc2_scores_phase2_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                    int64_t C, const int32_t* spos, const double* csum_all, int64_t P,
+                                    int64_t csum_stride, int64_t rows_per_rank, int64_t R_total,
+                                    const int64_t* rank_rows /* host [world] */, int world, int rank, void* ws,
+                                    size_t ws_bytes, void* v_T, void* f_T, float* total_f32, float* s_f32,
+                                    const float* blocks_all, int cap, void* stream);
 
 /* Step 3 of the sharded path: s_all_f32[F_total] = the all-gathered per-frame uniqueness scores
  * (fp32-widened T values); budgets are computed over all F_total frames, selection + gather only for

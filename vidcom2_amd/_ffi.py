@@ -66,6 +66,14 @@ _SIGNATURES = {
     "vc2_video_centre_blocks_round": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _sz, _vp, _i32, _i32, _vp],
     "vc2_video_centre_flagged": [_i64, _i64, _i64, _i32, _i64, _vp, _sz, _vp, _vp],
     "vc2_video_centre_finish_round": [_i64, _i64, _i64, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _i32, _i32, _i32, _vp],
+    "vc2_video_centre_blocks_ragged": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i32,
+                                       _i32, _vp, _sz, _vp, _i32, _vp],
+    "vc2_video_centre_blocks_round_ragged": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _sz,
+                                             _vp, _i32, _i32, _vp],
+    "vc2_video_centre_finish_round_ragged": [_i64, _i64, _i64, _i32, _i64, _vp, _i64, _vp, _i32, _i32, _vp, _sz, _vp, _i32,
+                                             _i32, _vp],
+    "vc2_scores_phase2_blocks_ragged": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i32,
+                                        _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "vc2_select_sharded": [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _dbl, _i32, _vp, _sz, _vp, _vp, _i64, _vp, _vp,
                            _vp, _vp],
     "vc2_multi_scale_gaussian": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, ctypes.POINTER(ctypes.c_double), _i32, _vp, _vp],

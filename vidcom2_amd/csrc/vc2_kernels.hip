@@ -2783,7 +2783,8 @@ __global__ __launch_bounds__(64) void k_video_centre(const double* __restrict__ 
 // The records are all-gathered (rank order = row order) and k_vc_finish runs the rest of torch's cascade over the
 // whole video: a straddling block is its rows' raw values added one by one in row order -- from as many ranks as it
 // meets (a rank with fewer rows than a block is all head); the video's last R_total % B rows (the cascade's tail) come
-// the same way.  Needs equal row counts per rank and the cascade's plain form (column in a full group of 32).  More
+// the same way.  Needs the cascade's plain form (column in a full group of 32).  Ranks with equal row counts are located by
+// division (k_vc_blocks / k_vc_finish); unequal ones through a prefix table (the _ragged kernels, same body).  More
 // flagged columns than a record buffer holds go in further rounds (slot offset j0).
 constexpr int kVcEdge = 64;
 __host__ __device__ inline int64_t vc_rec_floats(int64_t R_local) { return 2 * kVcEdge + R_local / 16 + 1; }
@@ -2806,10 +2807,10 @@ __device__ __forceinline__ int nth_flagged_column(const uint8_t* __restrict__ vf
 }
 
 template <int DT>
-__global__ __launch_bounds__(64) void k_vc_blocks(const uint8_t* __restrict__ vflag, int C, const void* __restrict__ x,
-                                                  int D, const int* __restrict__ cols, const int* __restrict__ spos,
-                                                  const float* __restrict__ den, int64_t R_local, int64_t row0, int lp,
-                                                  float* __restrict__ blocks_out, int j0) {
+__device__ __forceinline__ void vc_blocks_body(const uint8_t* __restrict__ vflag, int C, const void* __restrict__ x,
+                                               int D, const int* __restrict__ cols, const float* __restrict__ den,
+                                               int64_t R_local, int64_t row0, int lp, float* __restrict__ blocks_out,
+                                               int j0, int64_t rec_floats) {
   const int lane = threadIdx.x, j = blockIdx.y;                  // record j of this round = flagged column number j0 + j
   const int cc = nth_flagged_column(vflag, C, j0 + j, lane);
   if (cc < 0) return;
@@ -2818,7 +2819,7 @@ __global__ __launch_bounds__(64) void k_vc_blocks(const uint8_t* __restrict__ vf
   const int h = int(min<int64_t>(R_local, vc_head_rows(row0, B)));
   const int64_t nb = (R_local - h) >> lp;
   const int t = int(R_local - h - (nb << lp));
-  float* rec = blocks_out + int64_t(j) * vc_rec_floats(R_local);
+  float* rec = blocks_out + int64_t(j) * rec_floats;
   if (blockIdx.x == gridDim.x - 1) {                            // the raw edges
     if (lane < h) rec[lane] = xhat_at<DT>(x, lane, D, col, den);
     if (lane < t) rec[kVcEdge + lane] = xhat_at<DT>(x, h + (nb << lp) + lane, D, col, den);
@@ -2828,12 +2829,58 @@ __global__ __launch_bounds__(64) void k_vc_blocks(const uint8_t* __restrict__ vf
   if (b >= nb) return;
   rec[2 * kVcEdge + b] = block_sum_rows<DT>(x, D, col, den, h, 1, b << lp, lp);
 }
-
 template <int DT>
-__global__ __launch_bounds__(256) void k_vc_finish(const uint8_t* __restrict__ vflag, int C,
-                                                   const int* __restrict__ spos, const float* __restrict__ blocks_all,
-                                                   int world, int cap, int64_t R_local, int64_t R_total,
-                                                   float* __restrict__ vc, int* __restrict__ fragile_count, int j0) {
+__global__ __launch_bounds__(64) void k_vc_blocks(const uint8_t* __restrict__ vflag, int C, const void* __restrict__ x,
+                                                  int D, const int* __restrict__ cols, const int* __restrict__ spos,
+                                                  const float* __restrict__ den, int64_t R_local, int64_t row0, int lp,
+                                                  float* __restrict__ blocks_out, int j0) {
+  (void)spos;
+  vc_blocks_body<DT>(vflag, C, x, D, cols, den, R_local, row0, lp, blocks_out, j0, vc_rec_floats(R_local));
+}
+// unequal ranks: the records of all ranks share the stride of the rank with the most rows (one rectangular all-gather)
+template <int DT>
+__global__ __launch_bounds__(64) void k_vc_blocks_ragged(const uint8_t* __restrict__ vflag, int C,
+                                                         const void* __restrict__ x, int D, const int* __restrict__ cols,
+                                                         const float* __restrict__ den, int64_t R_local, int64_t row0,
+                                                         int lp, float* __restrict__ blocks_out, int j0,
+                                                         int64_t rec_floats) {
+  vc_blocks_body<DT>(vflag, C, x, D, cols, den, R_local, row0, lp, blocks_out, j0, rec_floats);
+}
+
+// Which rank holds video row r, and what that rank holds.  Equal ranks: a division.  Unequal ranks (the ragged entry
+// points): the prefix sums of the ranks' row counts, passed to the kernel by value (VC2_RAGGED_MAX_WORLD ranks at most) and
+// searched from LDS.  No rank is empty, so a row has one owner.
+struct VcEqualRanks {
+  int64_t R_local;
+  __device__ __forceinline__ int64_t owner(int64_t r) const { return r / R_local; }
+  __device__ __forceinline__ int64_t row0(int64_t w) const { return w * R_local; }
+  __device__ __forceinline__ int64_t rows(int64_t) const { return R_local; }
+  __device__ __forceinline__ int64_t rec_floats() const { return vc_rec_floats(R_local); }
+};
+constexpr int kVcMaxWorld = VC2_RAGGED_MAX_WORLD;
+struct VcRankTable { int64_t pre[kVcMaxWorld + 1]; int64_t rec; int world; };   // pre[w] = video row of rank w's first row
+struct VcRaggedRanks {
+  const int64_t* pre;                                             // [world + 1], in LDS
+  int64_t rec;
+  int world;
+  __device__ __forceinline__ int64_t owner(int64_t r) const {     // the last w with pre[w] <= r  (0 <= r < pre[world])
+    int lo = 0, hi = world;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (pre[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+  }
+  __device__ __forceinline__ int64_t row0(int64_t w) const { return pre[w]; }
+  __device__ __forceinline__ int64_t rows(int64_t w) const { return pre[w + 1] - pre[w]; }
+  __device__ __forceinline__ int64_t rec_floats() const { return rec; }
+};
+
+template <int DT, class Ranks>
+__device__ __forceinline__ void vc_finish_body(const uint8_t* __restrict__ vflag, int C, const int* __restrict__ spos,
+                                               const float* __restrict__ blocks_all, int cap, const Ranks rk,
+                                               int64_t R_total, float* __restrict__ vc, int* __restrict__ fragile_count,
+                                               int j0) {
   __shared__ float l1[kL1Cap + 4];
   __shared__ float tailv[kVcEdge];
   const int tid = threadIdx.x, lane = tid & 63, j = blockIdx.x;  // record j of this round = flagged column number j0 + j
@@ -2843,24 +2890,24 @@ __global__ __launch_bounds__(256) void k_vc_finish(const uint8_t* __restrict__ v
   const int sp = spos ? spos[cc] : cc;
   if (sp >= (C / group) * group) return;                        // row_sum's interleaved chains: not replayed here
   const int lp = cascade_lp(R_total), B = 1 << lp;
-  const int64_t rec = vc_rec_floats(R_local);
+  const int64_t rec = rk.rec_floats();
   auto record = [&](int64_t w) { return blocks_all + (w * cap + j) * rec; };
   // what rank w holds: h head rows (raw, the end of a block begun before it), nb complete blocks, t tail rows (raw)
-  auto head_of = [&](int64_t w) { return int(min<int64_t>(R_local, vc_head_rows(w * R_local, B))); };
+  auto head_of = [&](int64_t w) { return int(min<int64_t>(rk.rows(w), vc_head_rows(rk.row0(w), B))); };
   // the x^ value of video row r: raw in its rank's head or tail section (only asked for rows of straddling blocks)
   auto row_value = [&](int64_t r) -> float {
-    const int64_t w = r / R_local, off = r - w * R_local;
+    const int64_t w = rk.owner(r), off = r - rk.row0(w);
     const int h = head_of(w);
     if (off < h) return record(w)[off];
-    const int64_t nb = (R_local - h) >> lp;
+    const int64_t nb = (rk.rows(w) - h) >> lp;
     return record(w)[kVcEdge + (off - h - (nb << lp))];
   };
   // the level-0 sum of the video's block b: a rank's own complete block, or -- a block that meets two OR MORE ranks
   // (ranks with fewer rows than a block included) -- its rows one by one in row order
   auto block_value = [&](int64_t b) -> float {
-    const int64_t g0 = b << lp, w = g0 / R_local, off = g0 - w * R_local;
+    const int64_t g0 = b << lp, w = rk.owner(g0), off = g0 - rk.row0(w);
     const int h = head_of(w);
-    const int64_t nb = (R_local - h) >> lp;
+    const int64_t nb = (rk.rows(w) - h) >> lp;
     if (off >= h && ((off - h) & (B - 1)) == 0 && ((off - h) >> lp) < nb) return record(w)[2 * kVcEdge + ((off - h) >> lp)];
     float a = row_value(g0);
     for (int u = 1; u < B; ++u) a += row_value(g0 + u);
@@ -2888,6 +2935,25 @@ __global__ __launch_bounds__(256) void k_vc_finish(const uint8_t* __restrict__ v
       if (fragile_count) atomicSub(fragile_count, 1);            // one flagged column less that kept its exact mean
     }
   }
+}
+template <int DT>
+__global__ __launch_bounds__(256) void k_vc_finish(const uint8_t* __restrict__ vflag, int C,
+                                                   const int* __restrict__ spos, const float* __restrict__ blocks_all,
+                                                   int world, int cap, int64_t R_local, int64_t R_total,
+                                                   float* __restrict__ vc, int* __restrict__ fragile_count, int j0) {
+  (void)world;
+  vc_finish_body<DT>(vflag, C, spos, blocks_all, cap, VcEqualRanks{R_local}, R_total, vc, fragile_count, j0);
+}
+template <int DT>
+__global__ __launch_bounds__(256) void k_vc_finish_ragged(const uint8_t* __restrict__ vflag, int C,
+                                                          const int* __restrict__ spos,
+                                                          const float* __restrict__ blocks_all, int cap,
+                                                          const VcRankTable tab, int64_t R_total, float* __restrict__ vc,
+                                                          int* __restrict__ fragile_count, int j0) {
+  __shared__ int64_t pre[kVcMaxWorld + 1];
+  if (int(threadIdx.x) <= tab.world) pre[threadIdx.x] = tab.pre[threadIdx.x];
+  __syncthreads();
+  vc_finish_body<DT>(vflag, C, spos, blocks_all, cap, VcRaggedRanks{pre, tab.rec, tab.world}, R_total, vc, fragile_count, j0);
 }
 
 // a caller's Gaussian scales, passed BY VALUE to the kernels that take them (k_multi_scale_gaussian, and k_dist's
@@ -5416,6 +5482,134 @@ int vc2_scores_phase2_blocks(const void* x, int64_t F, int64_t N, int64_t D, int
   float* total = total_f32 ? total_f32 : wsp<float>(ws, p.o_total);
   float* s = s_f32 ? s_f32 : wsp<float>(ws, p.o_s);
   return launch_phase2(p, x, make_chanset(p, cols, spos, C), ws, v_T, f_T, total, s, st);
+}
+
+// ---- exchange 2b for ranks with UNEQUAL row counts (vc2.h): the layout of the video over the ranks comes as a host
+// array; from it this rank's row0 (prefix sum), the record stride all ranks share (the largest rank's) and the prefix
+// table k_vc_finish_ragged takes by value.  The flag / sweep launches are the equal-rank entry points' own.
+static bool vc_blocks_ok_ragged(const Plan& p, int64_t R_total, int strict) {
+  return strict != 0 && p.dt != VC2_F32 && cascade_modelled(R_total);
+}
+static int make_rank_table(const int64_t* rank_rows, int world, int rank, int64_t F, int64_t N, int64_t R_total,
+                           VcRankTable* tab) {
+  if (!rank_rows || world <= 0 || rank < 0 || rank >= world) return fail(VC2_ERR_ARG, "bad rank layout (world=%d, rank=%d)", world, rank);
+  if (world > kVcMaxWorld)
+    return fail(VC2_ERR_UNSUPPORTED, "ragged layout of %d ranks; at most %d are supported", world, kVcMaxWorld);
+  int64_t sum = 0, most = 0;
+  for (int w = 0; w < world; ++w) {
+    if (rank_rows[w] < N) return fail(VC2_ERR_ARG, "rank %d holds %lld rows: less than one frame", w, (long long)rank_rows[w]);
+    tab->pre[w] = sum;
+    sum += rank_rows[w];
+    most = std::max(most, rank_rows[w]);
+  }
+  for (int w = world; w <= kVcMaxWorld; ++w) tab->pre[w] = sum;
+  if (sum != R_total || rank_rows[rank] != F * N)
+    return fail(VC2_ERR_ARG, "rank layout: the ranks' rows sum to %lld (R_total %lld), rank %d holds %lld (F * N = %lld)",
+                (long long)sum, (long long)R_total, rank, (long long)rank_rows[rank], (long long)(F * N));
+  tab->rec = vc_rec_floats(most);
+  tab->world = world;
+  return VC2_OK;
+}
+
+int vc2_video_centre_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                   int64_t C, const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
+                                   int64_t rows_per_rank, int64_t R_total, const int64_t* rank_rows, int world, int rank,
+                                   void* ws, size_t ws_bytes, float* blocks_out, int cap, void* stream) {
+  if (!x || !csum_all || !blocks_out || P <= 0 || csum_stride < C || cap <= 0 || rows_per_rank < 0 ||
+      (rows_per_rank > 0 && (rows_per_rank % 2 || P % rows_per_rank)))
+    return fail(VC2_ERR_ARG, "bad video_centre_blocks_ragged arguments");
+  { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
+  VcRankTable tab;
+  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, &tab);
+  if (rc) return rc;
+  Plan p;
+  if ((rc = make_plan(F, N, D, dtype, &p, R_total / N))) return rc;
+  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ChanSet cs0 = make_chanset(p, cols, spos, C);
+  if (!vc_blocks_ok_ragged(p, R_total, cs0.strict)) return VC2_OK;   // nothing to exchange: phase 2 keeps the exact means
+  uint8_t* vflag = wsp<uint8_t>(ws, p.o_mask);
+  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_video_centre<DT>), dim3(unsigned(cdiv(C, 64))), dim3(64), 512 /* (replay_rows = 0: no LDS use) */, st,
+                                            csum_all, int(P), csum_stride, int(C), R_total, wsp<float>(ws, p.o_vc), x,
+                                            int(D), cols, spos, wsp<float>(ws, p.o_den), cs0.strict, 0,
+                                            wsp<int>(ws, p.o_ticket) + 5, (float*)nullptr, 0, (int*)nullptr, vflag,
+                                            int(rows_per_rank), margin_depth(R_total, cs0.strict), FrameStatSrc{},
+                                            (const float*)nullptr, 0));
+  const int lpv = cascade_lp(R_total);
+  const int64_t nb = p.R >> lpv;                               // (at most; one more grid column for the raw edges)
+  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks_ragged<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64),
+                                            0, st, vflag, int(C), x, int(D), cols, wsp<float>(ws, p.o_den), p.R,
+                                            tab.pre[rank], lpv, blocks_out, 0, tab.rec));
+  return check_launch("video_centre_blocks_ragged");
+}
+
+int vc2_video_centre_blocks_round_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                         int64_t C, const int32_t* spos, int64_t R_total, const int64_t* rank_rows,
+                                         int world, int rank, void* ws, size_t ws_bytes, float* blocks_out, int cap,
+                                         int col_offset, void* stream) {
+  if (!x || !blocks_out || cap <= 0 || col_offset < 0) return fail(VC2_ERR_ARG, "bad video_centre_blocks_round_ragged arguments");
+  { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
+  VcRankTable tab;
+  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, &tab);
+  if (rc) return rc;
+  Plan p;
+  if ((rc = make_plan(F, N, D, dtype, &p, R_total / N))) return rc;
+  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  if (!vc_blocks_ok_ragged(p, R_total, make_chanset(p, cols, spos, C).strict)) return VC2_OK;
+  const int lpv = cascade_lp(R_total);
+  const int64_t nb = p.R >> lpv;
+  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks_ragged<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64),
+                                            0, static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), x,
+                                            int(D), cols, wsp<float>(ws, p.o_den), p.R, tab.pre[rank], lpv, blocks_out,
+                                            col_offset, tab.rec));
+  return check_launch("video_centre_blocks_round_ragged");
+}
+
+int vc2_video_centre_finish_round_ragged(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
+                                         int64_t R_total, const int64_t* rank_rows, int world, int rank, void* ws,
+                                         size_t ws_bytes, const float* blocks_all, int cap, int col_offset, void* stream) {
+  if (!blocks_all || cap <= 0 || col_offset < 0) return fail(VC2_ERR_ARG, "bad video_centre_finish_round_ragged arguments");
+  VcRankTable tab;
+  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, &tab);
+  if (rc) return rc;
+  Plan p;
+  if ((rc = make_plan(F, N, D, dtype, &p, R_total / N))) return rc;
+  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish_ragged<DT>), dim3(unsigned(cap)), dim3(256), 0,
+                                            static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), spos,
+                                            blocks_all, cap, tab, R_total, wsp<float>(ws, p.o_vc),
+                                            wsp<int>(ws, p.o_ticket) + 5, col_offset));
+  return check_launch("video_centre_finish_round_ragged");
+}
+
+int vc2_scores_phase2_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                    int64_t C, const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
+                                    int64_t rows_per_rank, int64_t R_total, const int64_t* rank_rows, int world, int rank,
+                                    void* ws, size_t ws_bytes, void* v_T, void* f_T, float* total_f32, float* s_f32,
+                                    const float* blocks_all, int cap, void* stream) {
+  if (!x || !csum_all || !blocks_all || cap <= 0 || P <= 0 || csum_stride < C || rows_per_rank < 0 ||
+      (rows_per_rank > 0 && (rows_per_rank % 2 || P % rows_per_rank)))
+    return fail(VC2_ERR_ARG, "bad phase-2 arguments");
+  { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
+  VcRankTable tab;
+  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, &tab);
+  if (rc) return rc;
+  Plan p;
+  if ((rc = make_plan(F, N, D, dtype, &p, R_total / N))) return rc;
+  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const ChanSet cs0 = make_chanset(p, cols, spos, C);
+  // the records exist (vc2_video_centre_blocks_ragged wrote them) exactly when that call found the replay applicable;
+  // otherwise this is vc2_scores_phase2: exact means, counted
+  if (!vc_blocks_ok_ragged(p, R_total, cs0.strict))
+    return vc2_scores_phase2_blocks(x, F, N, D, dtype, cols, C, spos, csum_all, P, csum_stride, rows_per_rank, R_total, ws,
+                                    ws_bytes, v_T, f_T, total_f32, s_f32, nullptr, 0, 0, stream);
+  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish_ragged<DT>), dim3(unsigned(cap)), dim3(256), 0, st,
+                                            wsp<uint8_t>(ws, p.o_mask), int(C), spos, blocks_all, cap, tab, R_total,
+                                            wsp<float>(ws, p.o_vc), wsp<int>(ws, p.o_ticket) + 5, 0));
+  float* total = total_f32 ? total_f32 : wsp<float>(ws, p.o_total);
+  float* s = s_f32 ? s_f32 : wsp<float>(ws, p.o_s);
+  return launch_phase2(p, x, cs0, ws, v_T, f_T, total, s, st);
 }
 
 int vc2_scores(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,

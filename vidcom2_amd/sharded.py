@@ -1,16 +1,23 @@
 """Frame-sharded VidCom2 compression across the GPUs of one node.
 
-One process per GPU (torch.distributed, backend "nccl" = RCCL over xGMI).  Rank p holds frames
-[p*F_local, (p+1)*F_local) of ONE video.  The pass shards by frame with three tiny exchange steps --
+One process per GPU (torch.distributed, backend "nccl" = RCCL over xGMI).  Rank p holds a contiguous run of frames
+of ONE video: [p*F_local, (p+1)*F_local) with equal shards, [f0_p, f0_p + F_p) with unequal ones (any F_p >= 1;
+shard_frames() proposes a split).  The pass shards by frame with three tiny exchange steps --
 every message is <= a few hundred KB, i.e. latency-bound, so each is a single all-gather followed by
 a fixed-order local reduction (NOT an all-reduce: the fixed order makes every rank compute the same
 bits; the partials are CANONICAL -- cut at fixed frame boundaries and folded in one fixed order -- so the bits are also
-the same for every world size, and the same as the unsharded pass's, when each rank holds a multiple of 16 frames):
+the same for every world size and every split, and the same as the unsharded pass's, when each rank holds a multiple
+of 16 frames; with other splits the fp64 partials are cut elsewhere: every rank still has the same bits, the variances
+and centre sums equal the unsharded pass's up to fp64 rounding BEFORE they are rounded to T):
 
   after sweep 1   per 8-frame block statistics (mean, M2)  fp64 [F_l/8, 2, D] -> identical channel mask
   after sweep 2   per 16-frame sums of normalised tokens   fp64 [F_l/16, C]   -> identical video centre
   after sweep 3   per-frame uniqueness scores  -mean(v)    fp32 [F_local] -> global softmax budgets
                   (the RCCL all-gather BASELINE.json's north_star names)
+
+With unequal shards an exchange whose per-rank size differs (stat blocks, group sums, replay records, s) is padded to
+the largest rank's message -- the all-gather stays one rectangular collective -- and compacted on the device before the
+stage that consumes it; equal shards issue exactly the calls they always did.
 
 Kept rows stay sharded by frame (each rank returns the kept rows / indices of its own frames); the
 reference has no multi-GPU form of this path -- its only parallelism is document-level DP in the
@@ -32,6 +39,54 @@ from . import _ffi
 from ._ffi import DTYPE_CODE, check, lib, on_device, ptr, stream_ptr
 
 
+def shard_frames(F_total: int, world: int, align: int = 8) -> list:
+    """Frames per rank of a contiguous, balanced split of F_total frames over `world` ranks, every rank >= 1 frame.
+    When F_total >= align * world all ranks but the last hold a multiple of `align` frames (align = 8 keeps the
+    canonical stat blocks at 8 frames: the channel variances are then the unsharded pass's bits); otherwise the plain
+    balanced split (the first F_total % world ranks hold one frame more)."""
+    F_total, world, align = int(F_total), int(world), int(align)
+    if world < 1 or align < 1:
+        raise ValueError(f"shard_frames: world and align must be positive (got {world}, {align})")
+    if world > F_total:
+        raise ValueError(f"shard_frames: {world} ranks for {F_total} frames -- a rank without frames is not supported")
+    if F_total >= align * world:
+        units, extra = divmod(F_total // align, world)          # whole `align`-frame units, dealt out evenly
+        parts = [(units + (1 if p < extra else 0)) * align for p in range(world)]
+        parts[-1] += F_total % align
+    else:
+        q, r = divmod(F_total, world)
+        parts = [q + (1 if p < r else 0) for p in range(world)]
+    return parts
+
+
+def stat_block_frames(frames) -> int:
+    """Frames per stat block of exchange 1: the largest power of two <= 8 that divides EVERY rank's frame count, so that
+    every f0 is a multiple of it and the gathered blocks form one uniform grid of the video."""
+    return next(b for b in (8, 4, 2, 1) if all(f % b == 0 for f in frames))
+
+
+def pad_rows(t: torch.Tensor, n_max: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """t [n, ...] as the first rows of a zero-padded [n_max, ...] message (t itself when n == n_max)."""
+    if t.shape[0] == n_max:
+        return t
+    if out is None:
+        out = torch.zeros((n_max,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    out[: t.shape[0]].copy_(t)
+    return out
+
+
+def compact_index(counts, device) -> torch.Tensor:
+    """Row numbers, in rank order, of the ranks' real rows in a gathered [world * max(counts), ...] buffer."""
+    n_max = max(counts)
+    return torch.tensor([p * n_max + i for p, c in enumerate(counts) for i in range(c)], dtype=torch.int64, device=device)
+
+
+def compact_rows(gathered: torch.Tensor, index: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[world, n_max, ...] (padded messages in rank order) -> [sum(counts), ...]: one device gather, no host sync."""
+    flat = gathered.reshape((-1,) + tuple(gathered.shape[2:]))
+    return torch.index_select(flat, 0, index) if out is None else torch.index_select(flat, 0, index, out=out)
+
+
 @dataclass
 class ShardResult:
     rows: Optional[torch.Tensor]     # [K_local, D] kept rows of this rank's frames
@@ -45,20 +100,38 @@ class HipStages:
     """The five shard-local stages on the HIP kernels (include/vc2.h 'frame-sharded building blocks')."""
 
     def __init__(self, F: int, N: int, D: int, dtype, device, base_scale: float, gather: bool = True,
-                 vc_cap: int = 64):
+                 vc_cap: int = 64, frames=None, rank: int = 0):
+        """frames / rank: the layout of the video over the ranks (every rank's frame count, this rank's number).  None,
+        or equal counts: the equal-shard pass (F_total = world * F, set by ShardedCompressor).  Unequal counts: the buffers
+        that take part in an exchange are sized for the largest rank and exchange 2b goes through the ragged entry points."""
         self.F, self.N, self.D, self.dtype, self.device, self.base = F, N, D, dtype, torch.device(device), base_scale
         self.code = DTYPE_CODE[dtype]
         L = lib()
+        self.frames = [int(f) for f in frames] if frames is not None else None
+        self.rank = int(rank)
+        self.ragged = self.frames is not None and len(set(self.frames)) > 1
+        if self.frames is not None and (not 0 <= self.rank < len(self.frames) or self.frames[self.rank] != F
+                                        or min(self.frames) < 1):
+            raise ValueError(f"HipStages: rank {rank} with {F} frames does not fit the layout {self.frames}")
         self.ws = _ffi.workspace(F, N, D, dtype, self.device)
         # canonical partials (SURVEY.md §8e): per stat block of `bf` frames (mean, M2); per group of 16 frames the
         # sums of the normalised tokens.  bf = 8 whenever F is a multiple of 8 (then the gathered blocks are exactly
-        # the unsharded pass's blocks and every world size reduces to the same bits)
-        self.bf = next(b for b in (8, 4, 2, 1) if F % b == 0)
+        # the unsharded pass's blocks and every world size reduces to the same bits); unequal shards: the largest
+        # power of two that divides every rank's count
+        self.bf = stat_block_frames(self.frames if self.ragged else [F])
         self.stats = torch.empty((F // self.bf, 2, D), dtype=torch.float64, device=self.device)
         self.C = int(D * 0.5)                                   # int(x.shape[-1] * ratio), vidcom2.py:41
-        # exchange 2: per group of 16 frames the sums of x^ and, behind them, the groups' bounds of sum |x^|
-        self.csum = torch.zeros((2 * ((F + 15) // 16), self.C), dtype=torch.float64, device=self.device)
-        self.F_total = F                                        # set by ShardedCompressor (world * F)
+        # exchange 2: per group of 16 frames the sums of x^ and, behind them, the groups' bounds of sum |x^|.  Unequal
+        # shards: k_video_centre reads every rank's message as [half sums | half bounds], so a rank with fewer groups
+        # than the largest pads INSIDE each half (zero rows: they change neither the sums nor the bounds)
+        G = (F + 15) // 16
+        self._G, self._Gmax = G, max((f + 15) // 16 for f in self.frames) if self.ragged else G
+        self.csum = torch.zeros((2 * self._Gmax, self.C), dtype=torch.float64, device=self.device)
+        self._csum_raw = (torch.empty((2 * G, self.C), dtype=torch.float64, device=self.device)
+                          if G != self._Gmax else self.csum)
+        self.F_total = sum(self.frames) if self.ragged else F   # equal shards: set by ShardedCompressor (world * F)
+        # the layout as the ragged entry points take it: a host array of the ranks' row counts
+        self._rank_rows = (ctypes.c_int64 * len(self.frames))(*[f * N for f in self.frames]) if self.ragged else None
         self.var_f32 = torch.empty(D, dtype=torch.float32, device=self.device)
         self.mask = torch.empty(D, dtype=torch.uint8, device=self.device)
         self.cols = torch.empty(D, dtype=torch.int32, device=self.device)
@@ -75,18 +148,27 @@ class HipStages:
         self.vc_cap = int(vc_cap)                             # flagged columns whose blocks one exchange carries
         self.vc_replay = dtype != torch.float32
         # per flagged column: 64 + 64 raw edge values and the sums of this rank's complete blocks (include/vc2.h)
-        self.blocks = torch.zeros((self.vc_cap, 129 + F * N // 16), dtype=torch.float32, device=self.device)
+        # (unequal shards: every rank's records have the stride of the rank with the most rows)
+        self.blocks = torch.zeros((self.vc_cap, 129 + (max(self.frames) if self.ragged else F) * N // 16),
+                                  dtype=torch.float32, device=self.device)
         self.rows = torch.empty((self.cap, D), dtype=dtype, device=self.device) if gather else None
 
         # device pointers of the fixed buffers, resolved once: the per-pass host work is five C calls plus
         # three collectives, and that host time bounds the pass when it exceeds the ~0.3 ms of GPU work
         self._L = L
         self._p = {n: ptr(getattr(self, n)) for n in ("ws", "stats", "csum", "var_f32", "mask", "cols", "perm",
-                                                     "spos", "total", "s", "idx", "ks", "kout", "rows", "blocks")}
+                                                     "spos", "total", "s", "idx", "ks", "kout", "rows", "blocks",
+                                                     "_csum_raw")}
         self._ws_n = self.ws.numel()
 
     def _st(self):
         return stream_ptr(self.device)
+
+    def set_layout(self, frames, rank) -> None:
+        """What ShardedCompressor tells a stage object about unequal shards.  These stages are built for one layout."""
+        if [int(f) for f in frames] != self.frames or int(rank) != self.rank:
+            raise ValueError(f"HipStages was built for the layout {self.frames} (rank {self.rank}), not {list(frames)} "
+                             f"(rank {rank}): pass frames= and rank= to its constructor")
 
     def chan_stats(self, x):
         p = self._p
@@ -107,9 +189,12 @@ class HipStages:
     def phase1(self, x):
         p = self._p
         check(self._L.vc2_scores_phase1(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
-                                        p["perm"], p["var_f32"], self.F_total, p["ws"], self._ws_n, p["csum"],
+                                        p["perm"], p["var_f32"], self.F_total, p["ws"], self._ws_n, p["_csum_raw"],
                                         self._st()),
               "vc2_scores_phase1")
+        if self._G != self._Gmax:                               # fewer groups than the largest rank: pad inside each half
+            self.csum[: self._G].copy_(self._csum_raw[: self._G])
+            self.csum[self._Gmax: self._Gmax + self._G].copy_(self._csum_raw[self._G:])
         return self.csum
 
     def vc_blocks(self, x, csum_all, R_total, f0=0):
@@ -119,10 +204,19 @@ class HipStages:
         frame.  A block may meet any number of ranks (since round 4: ranks with fewer rows than a block included)."""
         from .vidcom2 import cascade_modelled
         Rl = self.F * self.N
-        if not self.vc_replay or _ffi.get_mode() != "torch" or not cascade_modelled(R_total) or R_total % Rl != 0:
+        if not self.vc_replay or _ffi.get_mode() != "torch" or not cascade_modelled(R_total):
             return None
         p = self._p
         parts = csum_all.reshape(-1, csum_all.shape[-1])
+        if self.ragged:
+            check(self._L.vc2_video_centre_blocks_ragged(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
+                                                         p["spos"], ptr(parts), parts.shape[0], parts.shape[1],
+                                                         self.csum.shape[0], R_total, self._rank_rows, len(self.frames),
+                                                         self.rank, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
+                                                         self._st()), "vc2_video_centre_blocks_ragged")
+            return self.blocks
+        if R_total % Rl != 0:
+            return None
         check(self._L.vc2_video_centre_blocks(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
                                               ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total,
                                               int(f0) * self.N, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
@@ -145,6 +239,13 @@ class HipStages:
 
     def vc_blocks_round(self, x, R_total, f0, col_offset):
         p = self._p
+        if self.ragged:
+            check(self._L.vc2_video_centre_blocks_round_ragged(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
+                                                               p["spos"], R_total, self._rank_rows, len(self.frames),
+                                                               self.rank, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
+                                                               int(col_offset), self._st()),
+                  "vc2_video_centre_blocks_round_ragged")
+            return self.blocks
         check(self._L.vc2_video_centre_blocks_round(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
                                                     R_total, int(f0) * self.N, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
                                                     int(col_offset), self._st()), "vc2_video_centre_blocks_round")
@@ -152,6 +253,12 @@ class HipStages:
 
     def vc_finish_round(self, R_total, blocks_all, col_offset):
         p = self._p
+        if self.ragged:
+            check(self._L.vc2_video_centre_finish_round_ragged(self.F, self.N, self.D, self.code, self.C, p["spos"], R_total,
+                                                               self._rank_rows, len(self.frames), self.rank, p["ws"],
+                                                               self._ws_n, ptr(blocks_all), self.vc_cap, int(col_offset),
+                                                               self._st()), "vc2_video_centre_finish_round_ragged")
+            return
         check(self._L.vc2_video_centre_finish_round(self.F, self.N, self.D, self.code, self.C, p["spos"], R_total, p["ws"],
                                                     self._ws_n, ptr(blocks_all), int(blocks_all.shape[0]), self.vc_cap,
                                                     int(col_offset), self._st()), "vc2_video_centre_finish_round")
@@ -163,6 +270,14 @@ class HipStages:
         world = -1 if vc_final else (0 if blocks_all is None else int(blocks_all.shape[0]))
         if vc_final:
             blocks_all = None
+        if self.ragged and blocks_all is not None:
+            check(self._L.vc2_scores_phase2_blocks_ragged(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
+                                                          p["spos"], ptr(parts), parts.shape[0], parts.shape[1],
+                                                          self.csum.shape[0], R_total, self._rank_rows, len(self.frames),
+                                                          self.rank, p["ws"], self._ws_n, None, None, p["total"], p["s"],
+                                                          ptr(blocks_all), self.vc_cap, self._st()),
+                  "vc2_scores_phase2_blocks_ragged")
+            return self.s
         check(self._L.vc2_scores_phase2_blocks(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
                                                ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total,
                                                p["ws"], self._ws_n, None, None, p["total"], p["s"],
@@ -206,7 +321,15 @@ def _all_gather(t: torch.Tensor, group, world: int, out: Optional[torch.Tensor] 
 
 
 class ShardedCompressor:
-    """Frame-sharded pass; every rank calls enqueue(x_local) + finish() collectively."""
+    """Frame-sharded pass; every rank calls enqueue(x_local) + finish() collectively.  F_local may differ between the
+    ranks (>= 1 each; N, D and the dtype must agree).  `frames` holds all ranks' counts, `f0` this rank's first frame,
+    `F_total` their sum.
+
+    Stage objects (`stages=`): with equal shards the protocol of HipStages' five methods as it always was.  With unequal
+    shards the object must have set_layout(frames, rank) -- called once, here -- and then: chan_stats returns
+    [F_local / bf, 2, D] with bf = stat_block_frames(frames) and select_channels takes the compacted [sum F_p / bf, 2, D];
+    phase1's and vc_blocks' messages have the same shape on every rank (the stage pads them for the largest rank);
+    phase2 returns [F_local] and select takes the compacted [F_total]."""
 
     def __init__(self, F_local: int, N: int, D: int, dtype, device, base_scale: float = 0.25, group=None,
                  stages=None, gather: bool = True, always_collective: bool = False):
@@ -218,19 +341,38 @@ class ShardedCompressor:
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if self.world > 1 else 0
         self.F, self.N, self.D = int(F_local), int(N), int(D)
+        if self.F < 1:
+            raise ValueError(f"ShardedCompressor: a rank needs at least one frame (got {F_local})")
+        self.frames = [self.F] * self.world
         if self.world > 1:
-            # every rank must bring the same number of frames (the canonical partials, the exchanges' message sizes and
-            # the replay blocks are cut on that assumption): say so instead of hanging in a mismatched collective
+            # the ranks may bring different numbers of frames, but one frame geometry and one dtype: say so instead of
+            # hanging in a mismatched collective
             fl = [None] * self.world
-            dist.all_gather_object(fl, (self.F, self.N, self.D), group=group)
-            if any(t != fl[0] for t in fl):
-                raise ValueError(f"ShardedCompressor: every rank must hold the same (frames, tokens per frame, width); got {fl}")
-        self.F_total = self.F * self.world
-        self.f0 = self.rank * self.F
-        self.stages = stages if stages is not None else HipStages(self.F, self.N, self.D, dtype, device, base_scale,
-                                                                  gather)
-        if isinstance(self.stages, HipStages):
+            dist.all_gather_object(fl, (self.F, self.N, self.D, str(dtype)), group=group)
+            if any(t[1:] != fl[0][1:] for t in fl) or any(t[0] < 1 for t in fl):
+                raise ValueError("ShardedCompressor: every rank must hold at least one frame and the same (tokens per "
+                                 f"frame, width, dtype); got (frames, tokens per frame, width, dtype) = {fl}")
+            self.frames = [int(t[0]) for t in fl]
+        self.ragged = len(set(self.frames)) > 1
+        self.F_total = sum(self.frames)
+        self.f0 = sum(self.frames[: self.rank])
+        if stages is not None:
+            self.stages = stages
+        elif self.ragged:
+            self.stages = HipStages(self.F, self.N, self.D, dtype, device, base_scale, gather, frames=self.frames,
+                                    rank=self.rank)
+        else:
+            self.stages = HipStages(self.F, self.N, self.D, dtype, device, base_scale, gather)
+        if self.ragged:
+            # the stage object has to cut its partials for THIS layout (stat blocks, padded group sums, record stride)
+            if not callable(getattr(self.stages, "set_layout", None)):
+                raise TypeError(f"ShardedCompressor: the ranks hold unequal frame counts {self.frames}, and the stage object "
+                                f"{type(self.stages).__name__} has no set_layout(frames, rank) method to take that layout")
+            self.stages.set_layout(self.frames, self.rank)
+        elif isinstance(self.stages, HipStages):
             self.stages.F_total = self.F_total
+        self._bf = stat_block_frames(self.frames)
+        self._cidx, self._pad, self._cat = {}, {}, {}
 
         self._gbuf = {}
 
@@ -248,6 +390,24 @@ class ShardedCompressor:
         b.record()
         self._xev.setdefault(key, []).append((a, b))
         return out
+
+    def _gather_rows(self, key: str, t: torch.Tensor, counts) -> torch.Tensor:
+        """An exchange whose message differs in size between the ranks (rank p brings counts[p] leading rows): padded to
+        the largest, one rectangular all-gather, compacted to [sum(counts), ...] in rank order on the device."""
+        n_max = max(counts)
+        if t.shape[0] != n_max:
+            buf = self._pad.get(key)
+            if buf is None or buf.shape[1:] != t.shape[1:] or buf.dtype != t.dtype or buf.device != t.device:
+                buf = self._pad[key] = torch.zeros((n_max,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+            t = pad_rows(t, n_max, buf)
+        got = self._gather(key, t)
+        idx = self._cidx.get(key)
+        if idx is None or idx.device != t.device:
+            idx = self._cidx[key] = compact_index(counts, t.device)
+        out = self._cat.get(key)
+        if out is None or out.shape[1:] != t.shape[1:] or out.dtype != t.dtype or out.device != t.device:
+            out = self._cat[key] = torch.empty((sum(counts),) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+        return compact_rows(got, idx, out)
 
     def _collect(self, t: torch.Tensor, buf: torch.Tensor) -> torch.Tensor:
         if self.world == 1:                                # (always_collective: the collective itself, one rank)
@@ -285,7 +445,10 @@ class ShardedCompressor:
     def _enqueue(self, x_local: torch.Tensor) -> None:
         st = self.stages
         R_total = self.F_total * self.N
-        stats_all = self._gather("stats", st.chan_stats(x_local))               # exchange 1: [W, 2, D] fp64
+        if self.ragged:                                                          # exchange 1: [sum nb_p, 2, D] fp64
+            stats_all = self._gather_rows("stats", st.chan_stats(x_local), [f // self._bf for f in self.frames])
+        else:
+            stats_all = self._gather("stats", st.chan_stats(x_local))           # exchange 1: [W, 2, D] fp64
         st.select_channels(stats_all, R_total)
         csum_all = self._gather("csum", st.phase1(x_local))                     # exchange 2: [W, D] fp64
         blocks = st.vc_blocks(x_local, csum_all, R_total, self.f0) if hasattr(st, "vc_blocks") else None
@@ -302,7 +465,7 @@ class ShardedCompressor:
             s_loc = st.phase2(x_local, csum_all, R_total, self._gather("blocks", blocks))
         else:
             s_loc = st.phase2(x_local, csum_all, R_total)
-        s_all = self._gather("s", s_loc)                                         # exchange 3: [W, F_local]
+        s_all = self._gather_rows("s", s_loc, self.frames) if self.ragged else self._gather("s", s_loc)   # exchange 3: [W, F_local]
         st.select(x_local, s_all.reshape(-1), self.f0)
 
     def finish(self) -> ShardResult:
