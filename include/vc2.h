@@ -52,9 +52,13 @@ const char* vc2_version(void);
 
 /* Accumulation semantics of the reference's fp32-accumulated reductions in half precision (token L2 norm,
  * squared-distance row sums, centre means):
- *   4 (default)  "torch order": wherever the exactly computed value lies within a few fp32-ulps (128 / 48) of a T rounding
- *                boundary, torch's own CPU accumulation order (8 interleaved fp32 chains over the variance-sorted
- *                channels / cascade sum) is replayed for that token -> bit-exact to the CPU reference.  FRAME-centre means
+ *   4 (default)  "torch order": wherever the exactly computed value lies within a margin of fp32-ulps of a T rounding
+ *                boundary, torch's own CPU accumulation order (bf16: 8 interleaved fp32 chains over the variance-sorted
+ *                channels, fp16: one sequential chain / cascade sum) is replayed for that token -> bit-exact to the CPU
+ *                reference.  The margins (vc2_selftest_margins): squared-distance sums 48, a bound on the cascade's error;
+ *                norms max(128, bound of torch's chains) for bf16, 128 for fp16 -- a bound up to 254 scored channels and an
+ *                EMPIRICAL margin beyond: an fp16 row on which every add of torch's chain errs the same way (built inputs
+ *                only; ordinary data errs by ~10 ulps) keeps the exactly rounded norm in this mode.  Mode 3 has the bound.  FRAME-centre means
  *                (round 6): the model shapes -- 16-bit inputs, D = 1024 / 3584 / 4096, frames of <= 512 tokens, every frame
  *                workgroup resident -- add every frame's x^ in torch's OWN order inside sweep 2 (16-row blocks, fp32, the
  *                outer-sum cascade of SumKernel.cpp): the frame means are the reference's bits by construction, no margin,
@@ -66,7 +70,8 @@ const char* vc2_version(void);
  *                adversarial `cancel` ones) and every soak case.
  *   0            "exact": every reduction correctly rounded (DESIGN.md "Numerics contract").
  *   3            "proven": a PROVEN bound decides which centre means are replayed (forward error bound of torch's
- *                cascade relative to sum |x^|, bounded from sweep 1's statistics): flags 50x more means, costs ~45 %
+ *                cascade relative to sum |x^|, bounded from sweep 1's statistics) and which fp16 norms (C / 2 + 1 ulps for C
+ *                scored channels: a fifth of the rows at C = 1792): flags 50x more means, costs ~45 %
  *                more time (256 against 178 us per pass at the target shape, round 5; with VC2_S2_ORD=0); the test-suite runs every fixture
  *                in it as well and asserts the same results.
  *   1            "fast" (the default of rounds 1-3, now opt-in): the 16-ulp margin alone for all centre means.  ~1 %
@@ -489,6 +494,21 @@ int vc2_selftest_force_guard(int frame);
  * workgroups (0: the shape has no ORD geometry -- the row-interleaved sweep with margins and replays runs), or an error (< 0).
  * The test-suite checks that the pieces tile every frame exactly once and fit the resident workgroup slots. */
 int vc2_selftest_ord_pieces(int64_t F, int64_t N, int64_t D, int dtype, int32_t* out5_host, int64_t cap);
+
+/* Host arithmetic only (no device call): the replay margins, in fp32-ulps, that a pass over C scored channels of this
+ * dtype uses in `mode` (the codes of vc2_set_mode) -- out2 = host int32[2] {norm, squared-distance sum}; {-1, -1} where
+ * nothing is replayed (mode 0, fp32).  A sum whose exactly computed value lies within the margin of a T rounding boundary
+ * is replayed in torch's order.  These are the parts that cover TORCH'S accumulation error; the sweeps add the bound of
+ * their own fp32 accumulation on top.  With k = the roundings along the deepest path of torch's sum of C non-negative
+ * terms, torch's sum is within k 2^-24 (relative) of the exact one:
+ *   norm      bf16: 8 interleaved chains, k = 2 (C / 16) + 7 + C % 16; fp16: ONE sequential chain, k = C.  After the
+ *             square root: k / 2 + 1 ulps.  The margin is max(128, that bound) for bf16 in every mode and for fp16 in
+ *             modes 3 and 2; for fp16 in modes 4 and 1 it is 128 whatever C is -- a bound up to C = 254 only, an
+ *             empirical margin beyond (what the bound would cost, and the inputs that need it).
+ *   distance  SumKernel.cpp's cascade: k <= 33 up to C = 4096 (37 up to 8192), so k + 1 <= 38 ulps; the margin is 48 in
+ *             every mode.
+ * The test-suite derives both bounds from the oracle's summation structure and checks the margins against them. */
+int vc2_selftest_margins(int64_t C, int dtype, int mode, int32_t* out2_host);
 
 #ifdef __cplusplus
 }

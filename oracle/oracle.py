@@ -23,7 +23,7 @@ __all__ = [
     "compute_gaussian_scores", "gaussian_debug", "fuse", "compute_scales", "compute_ks",
     "select_outlier_indices", "map_linear_offset", "map_grid_vid", "compress_indices",
     "vidcom2_compression", "set_num_threads", "exp_T", "gaussian_scores_sharded", "set_mode",
-    "multi_scale_gaussian",
+    "multi_scale_gaussian", "norm_torch_order", "sum_torch_order",
 ]
 
 
@@ -148,6 +148,24 @@ def multi_scale_gaussian(x: torch.Tensor, center: torch.Tensor, alphas) -> torch
     _chk(_L().vc2o_multi_scale_gaussian(_p(xx), _i64(F * N), _i64(C), _DT[x.dtype], _p(cc), _i64(cc.shape[0]),
                                         _i64(N), two_a, ctypes.c_int(len(alphas)), _p(out)), "multi_scale_gaussian")
     return out
+
+
+def norm_torch_order(row: torch.Tensor, dtype: torch.dtype) -> float:
+    """sqrt(sum row^2) of one row of T values (given widened to fp32, in torch's channel order) as torch's CPU norm
+    accumulates it for `dtype` -- the fp32 result before the cast to T."""
+    row = _prep(row.to(torch.float32))
+    fn = _L().vc2o_norm_torch_order
+    fn.restype = ctypes.c_float
+    return float(fn(_p(row), _i64(row.numel()), _DT[dtype]))
+
+
+def sum_torch_order(row: torch.Tensor, dtype: torch.dtype) -> float:
+    """sum(row) of one row of T values (widened to fp32) as torch's CPU cascade sum adds it for `dtype` -- the fp32
+    result before the cast to T."""
+    row = _prep(row.to(torch.float32))
+    fn = _L().vc2o_sum_torch_order
+    fn.restype = ctypes.c_float
+    return float(fn(_p(row), _i64(row.numel()), _DT[dtype]))
 
 
 def fuse(v: torch.Tensor, f: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

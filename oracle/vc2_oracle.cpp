@@ -252,6 +252,12 @@ extern "C" {
 // 0 = exact accumulation (default), 1 = torch's CPU accumulation order for the L2 norm and the row sums
 int vc2o_set_mode(int mode) { g_mode = mode; return 0; }
 
+// The two accumulation orders on their own (tests/test_replay_margins.py measures their error against exact sums):
+// v = n fp32 values (the widened T values of one row, in the order torch meets them) -> torch's fp32 result, before the
+// cast to T.  norm: sqrt(sum v^2) as norm_kernel_tensor_iterator_impl adds it; sum: cascade_sum.
+float vc2o_norm_torch_order(const float* v, int64_t n, int dt) { return norm_torch_order(v, n, dt); }
+float vc2o_sum_torch_order(const float* v, int64_t n, int dt) { return sum_torch_order(v, n, dt); }
+
 // vidcom2.py:40  variances = x.var(dim=0, unbiased=False)  -> T[D]
 int vc2o_chan_var(const void* x, int64_t R, int64_t D, int dt, void* var_out) {
   std::vector<double> s(Z(D), 0.0), m2(Z(D), 0.0);

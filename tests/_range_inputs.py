@@ -8,6 +8,8 @@ A case here is synth.make(...) plus a short list of edits that can be written as
     {"op": "scale", "e": E, "rows": [..] | null}                          x[rows] *= 2^E   (null: every row)
     {"op": "set", "rows": [..] | null, "cols": [..] | null, "value": v}   x[rows, cols] = v   (a T value, "inf", "nan")
     {"op": "add", "cols": [..], "value": c}                               x[:, cols] += c
+    {"op": "pattern", "rows": [..] | null, "cols": [..] | null, "head": [..], "tail": [..]}
+                                   x[rows, cols[j]] = head[j] for j < len(head), else tail[j % len(tail)]
 
 Each edit is done in fp64 and rounded to T once (a power-of-two scaling is exact unless it leaves T's normal range).
 The exponents are chosen from the data (design_cases): where a clip's selected-channel norms sit decides E.  `premise`
@@ -43,6 +45,10 @@ def apply(x: torch.Tensor, ops) -> torch.Tensor:
             blk = torch.full_like(blk, float(o["value"]))
         elif o["op"] == "add":
             blk = blk + float(o["value"])
+        elif o["op"] == "pattern":
+            head, tail = [float(v) for v in o["head"]], [float(v) for v in o["tail"]]
+            line = [head[j] if j < len(head) else tail[j % len(tail)] for j in range(blk.shape[1])]
+            blk = torch.tensor(line, dtype=torch.float64).expand_as(blk)
         else:
             raise ValueError(o["op"])
         y[rows[:, None], cols[None, :]] = blk.to(y.dtype)

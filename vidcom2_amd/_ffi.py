@@ -88,6 +88,7 @@ _SIGNATURES = {
     "vc2_selftest_counters": [_vp, _i32],
     "vc2_selftest_force_guard": [_i32],
     "vc2_selftest_ord_pieces": [_i64, _i64, _i64, _i32, _vp, _i64],
+    "vc2_selftest_margins": [_i64, _i32, _i32, _vp],
     "vc2_last_error": [],
     "vc2_version": [],
 }
@@ -213,8 +214,8 @@ MODE_CODE = {"exact": 0, "torch": 4, "torch_fast": 1, "torch_proven": 3, "torch_
 
 def set_mode(mode: str) -> None:
     """'torch' (default): bit-exact to the CPU reference in half precision (replays torch's fp32 accumulation
-    order where it decides a rounding); 'exact': every reduction correctly rounded; 'torch_proven': proven margins for
-    all centre means (~45 % slower); 'torch_fast': empirical margins only (opt-in, no parity claim under cancellation).
+    order where it decides a rounding; for fp16 token norms within an empirical margin); 'exact': every
+    reduction correctly rounded; 'torch_proven': proven margins for all centre means and fp16 norms (~45 % slower); 'torch_fast': empirical margins only (opt-in, no parity claim under cancellation).
     get_mode() answers 'torch' for all torch modes."""
     check(lib().vc2_set_mode(MODE_CODE[mode]), "vc2_set_mode")
 

@@ -969,15 +969,48 @@ __device__ __forceinline__ void load_col_offsets(const int* __restrict__ cols, i
 // norm_kernel_tensor_iterator_impl, SumKernel.cpp cascade_sum; pinned in oracle/vc2_oracle.cpp mode 1).
 // Their fp32 noise (<~1e-6 relative) changes the T-rounded result only when the exact value sits that
 // close to a T rounding boundary.  So: compute exactly (fp64), and only when the exact value is within
-// kFragileUlps fp32-ulps of a boundary replay torch's order for that token -- a few tokens per thousand.
-constexpr int kFragileUlpsNorm = 128;   // >= worst-case bound of the 8-chain FMA norm (232 * 2^-24 on the sum)
+// a margin of fp32-ulps of a boundary replay torch's order for that token -- a few tokens per thousand.
+//
+// The norm margin (norm_margin_ulps).  A sum of non-negative terms whose deepest path has k fp32 roundings is within
+// k * 2^-24 (relative) of the exact sum; the (correctly rounded) square root halves that, and v * 2^-24 < ulp(v): torch's
+// norm is within k / 2 + 1 fp32-ulps of RN_f32 of the exact one (norm_bound_ulps; + 1: the two final roundings).  k is
+//   bf16: 2 * (C / 16) + 7 + C % 16  -- element p goes to chain p % 8 (C / 8 fused multiply-adds per chain for whole
+//         16-element vectors), the chains are added 0..7, the C % 16 tail after: 231 at C = 1792 (bound 117), 263 at
+//         C = 2048 (133), 519 at C = 4096 (261);
+//   fp16: C  -- ATen's generic path is ONE sequential chain: 897 at C = 1792, 2049 at C = 4096.
+// Both are reached to within a few ulps by rows built for it (every small square absorbed by the chain's running sum:
+// tests/_margin_inputs.py, 223 of 261 ulps for bf16 at C = 4096, C / 4 for fp16).  kFragileUlpsNorm = 128 is that bound
+// for bf16 up to C = 1976 and for fp16 up to C = 254 only.  So:
+//   bf16, every "torch order" mode: max(128, bound) -- at C = 4096 the bound flags 0.8 % of the rows;
+//   fp16, mode 3 ("proven") and debug mode 2: max(128, bound);
+//   fp16, modes 4 / 1: 128, an EMPIRICAL margin from C = 255 on.  The bound would queue C / 8192 of the rows (22 % at
+//         C = 1792) for a sequential replay of C dependent fused multiply-adds each.  On ordinary data torch's chain
+//         errs by ~10 ulps (random-signed roundings); a row that needs more has to be built (a large head, then squares
+//         below half an ulp of the running sum) -- the default mode returns the exactly rounded norm for it, mode 3
+//         the reference's (tests/test_replay_margins.py).
+constexpr int kFragileUlpsNorm = 128;
+__host__ __device__ constexpr int norm_chain_depth(int dt, int C) {
+  return dt == VC2_F16 ? C : 2 * (C / 16) + 7 + C % 16;
+}
+__host__ __device__ constexpr int norm_bound_ulps(int dt, int C) { return (norm_chain_depth(dt, C) + 1) / 2 + 1; }
+__host__ __device__ constexpr int norm_margin_ulps(int dt, int C, int strict) {
+  const int b = norm_bound_ulps(dt, C);
+  const bool bounded = dt != VC2_F16 || strict == 3 || strict == 2;
+  return bounded && b > kFragileUlpsNorm ? b : kFragileUlpsNorm;
+}
 // That margin presumes torch's fp32 sum of squares is finite.  From 2^-12 (relative) below FLT_MAX on -- far wider than the
-// chains' 232 * 2^-24 -- torch's sum may overflow: its norm is inf and x^ = +-0 (NaN for an inf element) where the exact
+// chains' k * 2^-24 -- torch's sum may overflow: its norm is inf and x^ = +-0 (NaN for an inf element) where the exact
 // norm gives finite quotients.  Only sweep 2's exact path meets such rows (the fast paths' windows stay far below): in
 // 16-bit "torch order" mode they go to k_norm_fix's replay as well; fp32 rows, which have no replay, take the norm inf
 // where the exact sum rounds to inf in fp32.
 constexpr double kSumSqOverflow = 3.4028234663852886e38 * (1.0 - 1.0 / 4096.0);
-constexpr int kFragileUlpsDist = 48;    // >= worst-case bound of the cascade sum (~42 fp32 adds per lane)
+// The distance margin: the deepest path of torch's cascade sum (sum_torch_order) of C non-negative terms has at most 33
+// roundings up to C = 4096, 37 up to 8192 (the halves of a 16-element chunk, 15 adds at level 0, a level-1 add per 16
+// loads, the four interleaved vectors, up to three odd vectors, the eight lanes; a first add into an empty accumulator
+// is exact and the C % 16 tail is shorter): torch's sum is within 37 fp32-ulps of the exact one, 38 with the rounding
+// of ours (tests/test_replay_margins.py walks the oracle's cascade for every C).  A bound in every mode.
+constexpr int kFragileUlpsDist = 48;
+__host__ __device__ constexpr int dist_margin_ulps(int, int, int) { return kFragileUlpsDist; }
 
 template <int DT> __device__ __forceinline__ bool near_T_boundary(float y, int margin) {
   if constexpr (DT == VC2_F32) {
@@ -1398,7 +1431,7 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
       const bool exact_div = __any(span.h.x > kBf16SpanLen || span.h.y > kBf16SpanLen) != 0;
       if (!exact_div) {
         const float nrm32 = float(sqrt(double(wave_sum_bcast_f32(ssq))));   // correctly rounded fp32 square root
-        const float dn = finish_norm(nrm32, kFragileUlpsNorm + acc_norm_ulps(NPLB), false);
+        const float dn = finish_norm(nrm32, norm_margin_ulps(DT, C, strict) + acc_norm_ulps(NPLB), false);
         const float r = __builtin_amdgcn_rcpf(dn);
         if (lane == 0 && rflag) rflag[row] = 0;
 #pragma unroll
@@ -1416,7 +1449,7 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
     }
     if (!done) {
       float nrm32;
-      int margin = kFragileUlpsNorm;
+      int margin = norm_margin_ulps(DT, C, strict);
       bool ovf = false;
       if constexpr (ACC == 1 && DT != VC2_BF16) {
         float s0 = 0.f, s1 = 0.f;
@@ -1426,7 +1459,7 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
           if (i & 1) s1 = fmaf(xv[i], xv[i], s1); else s0 = fmaf(xv[i], xv[i], s0);
         }
         nrm32 = float(sqrt(double(wave_sum_bcast_f32(s0 + s1))));
-        margin = kFragileUlpsNorm + acc_norm_ulps(NPLB);
+        margin += acc_norm_ulps(NPLB);
       } else {
         double t = 0.0;
 #pragma unroll
@@ -1650,7 +1683,7 @@ __global__ __launch_bounds__(kRowWaves * 64, kS2Waves) void k_norm_colsum2(const
   }
   typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
   typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-  const int margin_fast = kFragileUlpsNorm + acc_norm_ulps(NPLB);
+  const int margin_exact = norm_margin_ulps(DT, C, strict), margin_fast = margin_exact + acc_norm_ulps(NPLB);
 
   constexpr int RS = ORD ? 1 : kRowWaves;                          // the wave's rows: r0 + RS i, i < cnt
   f2_t chain[ORD ? NP : 1];                                       // (ORD) the fp32 chains of the block under way
@@ -1812,7 +1845,7 @@ __global__ __launch_bounds__(kRowWaves * 64, kS2Waves) void k_norm_colsum2(const
           if constexpr (ORD != 0) chain[k] = pk_add_f32(chain[k], (f2_t){fa, fb});
           if (k + 1 < NP) asm volatile("" : "+v"(XA[k + 1]), "+v"(XB[k + 1]));
         }
-        meta = ((strict == 2 || t2 >= kSumSqOverflow || near_T_boundary<DT>(n32, kFragileUlpsNorm)) ? 1u : 0u) | 2u;
+        meta = ((strict == 2 || t2 >= kSumSqOverflow || near_T_boundary<DT>(n32, margin_exact)) ? 1u : 0u) | 2u;
       }
       if (lane == (i & 63)) { pk_dn = dn; pk_meta = meta; }
       if ((i & 63) == 63) flush(i - 63, 64);
@@ -3242,7 +3275,7 @@ __global__ __launch_bounds__(kRowWaves * 64, 1) void k_dist(const void* __restri
   using acc_t = typename std::conditional<ACC == 0, double, float>::type;
   float res_v = 0.f, res_f = 0.f;
   uint32_t res_flag = 0u;
-  const int margin = ACC == 0 ? kFragileUlpsDist : kFragileUlpsDist + acc_dist_ulps(NPLB);
+  const int margin = dist_margin_ulps(DT, C, strict) + (ACC == 0 ? 0 : acc_dist_ulps(NPLB));
   auto settle = [&](float dvv, float dff, int it) {               // one row's two sums -> lane `it`
     // rare: a sum within a few fp32 ulps of a T rounding boundary, where torch's own fp32 accumulation order
     // decides the result -> phase 2
@@ -6155,6 +6188,16 @@ int vc2_selftest_ord_pieces(int64_t F, int64_t N, int64_t D, int dtype, int32_t*
     }
   }
   return n;
+}
+
+int vc2_selftest_margins(int64_t C, int dtype, int mode, int32_t* out2_host) {
+  if (!out2_host) return fail(VC2_ERR_ARG, "null pointer");
+  if (C <= 0 || C > 8192 || mode < 0 || mode > 4 || dtype < VC2_F32 || dtype > VC2_F16)
+    return fail(VC2_ERR_ARG, "vc2_selftest_margins: C in 1..8192, dtype 0..2, mode 0..4");
+  const bool replays = mode != 0 && dtype != VC2_F32;            // (make_chanset: strict = the mode, 16-bit inputs only)
+  out2_host[0] = replays ? norm_margin_ulps(dtype, int(C), mode) : -1;
+  out2_host[1] = replays ? dist_margin_ulps(dtype, int(C), mode) : -1;
+  return VC2_OK;
 }
 
 int vc2_profile_enable(int on) {
