@@ -235,6 +235,30 @@ int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
                      int64_t* K_out, void* v_T, void* f_T, const void* tail, int64_t tail_rows, int flags,
                      int64_t* K_host, const vc2_pass_params* params, void* stream);
 
+/* vc2_compress_ex3 with the dtype the pass SCORES in, apart from the dtype x is stored in (vidcom2.py:15-36 applied to
+ * the widened input x.float(), without materialising it).
+ *   score_dtype == dtype                               exactly vc2_compress_ex3 (which forwards here): the same launches, the same bits
+ *   score_dtype == VC2_F32, dtype VC2_BF16 / VC2_F16   the rows are loaded as 16-bit values and widened in registers; every op of
+ *             the reference then rounds to fp32, as in the pass over fp32 inputs: fp64 reductions, F.normalize's eps as the
+ *             fp32 1e-12 (a zero row scores like the reference on x.float(), not NaN as native fp16 does), the fp32 norm
+ *             overflow rule, fp32 budgets, 64-bit selection words -- and no "torch order" replays: vc2_set_mode only
+ *             decides what it decides for fp32 inputs.  The result stands to the reference on x.float() where the
+ *             fp32-input pass stands to the reference on fp32 inputs: equal budgets, equal kept indices outside score ties
+ *             below the fp32 reduction noise, scores within 1e-6.
+ *   anything else                                      VC2_ERR_ARG; nothing is enqueued.
+ * In the fp32-scored pass v_T / f_T, when requested, are FLOAT[F, N]; out_rows, tail and gather_src stay in `dtype` (the row
+ * gather copies 16-bit rows); ks, idx_out, K_out, the host mirror words, flags (VC2_FLAG_HAVE_STATS: vc2_pool_stats' partials
+ * are arithmetic-neutral fp64 sums of the stored values), params and map_mode / grid_h behave as in vc2_compress_ex3.  Row-width
+ * and channel limits are those of the storage dtype (D <= 8192, D % 8 == 0 for the vector path).  The workspace of
+ * vc2_workspace_bytes(F, N, D, dtype) serves both passes: the fp32-scored one lays out the same arrays and needs none of
+ * the replay engine's.
+ * The stage entry points and the frame-sharded ones keep one dtype. */
+int vc2_compress_ex4(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale,
+                     int map_mode, int64_t grid_h, const void* gather_src, int64_t gather_rows,
+                     void* ws, size_t ws_bytes, void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks,
+                     int64_t* K_out, void* v_T, void* f_T, const void* tail, int64_t tail_rows, int flags,
+                     int64_t* K_host, const vc2_pass_params* params, int score_dtype, void* stream);
+
 /* ---- upstream fusion: LLaVA's get_2dPool (llava/model/llava_arch.py:171-190) + sweep 1 -------
  * xin T[F, H*W, D] (the projector output, token-major) -> x_out T[F, h*w, D] = its 2x2 pool, and the sweep-1
  * channel-statistics partials of x_out in ws (workspace of vc2_workspace_bytes(F, h*w, D)): the pooled tensor is

@@ -43,6 +43,8 @@ _SIGNATURES = {
                          _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp],
     "vc2_compress_ex3": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
                          _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "vc2_compress_ex4": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
+                         _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp],
     "vc2_wait_host_count": [_vp, _dbl],
     "vc2_pool_out_tokens": [_i64, _i64, _i32, _vp, _vp],
     "vc2_pool_stats": [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp],

@@ -16,10 +16,24 @@ namespace vc2 {
 
 constexpr int kWave = 64;
 
+// A kernel's DT names two things: how a row is STORED (element size, vector width, loads, the row gather) and where its
+// ARITHMETIC rounds (rnT, the means, the budgets, the score outputs, the replay engine).  For the three public dtypes the
+// two are the same.  Two library-internal codes (never part of vc2.h) pair 16-bit storage with fp32 arithmetic: the pass of
+// vc2_compress_ex4 with score_dtype = VC2_F32, i.e. the reference applied to x.float() without the fp32 copy.
+//   ST<DT> = the storage dtype, AT<DT> = the arithmetic dtype; st_of / at_of: the same for a run-time code.
+constexpr int VC2_BF16_A32 = 3;      // bf16 rows, fp32 arithmetic
+constexpr int VC2_F16_A32 = 4;       // fp16 rows, fp32 arithmetic
+__host__ __device__ constexpr int st_of(int dt) { return dt == VC2_BF16_A32 ? VC2_BF16 : dt == VC2_F16_A32 ? VC2_F16 : dt; }
+__host__ __device__ constexpr int at_of(int dt) { return (dt == VC2_BF16_A32 || dt == VC2_F16_A32) ? VC2_F32 : dt; }
+template <int DT> constexpr int ST = st_of(DT);
+template <int DT> constexpr int AT = at_of(DT);
+
 template <int DT> struct Tr;
 template <> struct Tr<VC2_F32>  { static constexpr int ES = 4; static constexpr int VEC = 4; };
 template <> struct Tr<VC2_BF16> { static constexpr int ES = 2; static constexpr int VEC = 8; };
 template <> struct Tr<VC2_F16>  { static constexpr int ES = 2; static constexpr int VEC = 8; };
+template <> struct Tr<VC2_BF16_A32> : Tr<VC2_BF16> {};      // (storage traits)
+template <> struct Tr<VC2_F16_A32> : Tr<VC2_F16> {};
 
 // ---- RN_T(fp32) widened to fp32 ------------------------------------------------------
 template <int DT> __device__ __forceinline__ float rnT(float v);
@@ -30,11 +44,13 @@ template <> __device__ __forceinline__ float rnT<VC2_BF16>(float v) {
 template <> __device__ __forceinline__ float rnT<VC2_F16>(float v) {
   return static_cast<float>(static_cast<_Float16>(v));      // v_cvt_f16_f32 (RNE) + v_cvt_f32_f16
 }
+template <> __device__ __forceinline__ float rnT<VC2_BF16_A32>(float v) { return v; }   // (arithmetic: fp32)
+template <> __device__ __forceinline__ float rnT<VC2_F16_A32>(float v) { return v; }
 
 // RN_T of two values at once (one v_cvt_pk_* instead of two)
 template <int DT> __device__ __forceinline__ void rnT2(float a, float b, float& ra, float& rb) {
   typedef float f2_t __attribute__((ext_vector_type(2)));
-  if constexpr (DT == VC2_F32) { ra = a; rb = b; }
+  if constexpr (AT<DT> == VC2_F32) { ra = a; rb = b; }
   else if constexpr (DT == VC2_BF16) {
     typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
     const f2_t w = __builtin_convertvector(__builtin_convertvector((f2_t){a, b}, b2_t), f2_t);
@@ -49,7 +65,7 @@ template <int DT> __device__ __forceinline__ void rnT2(float a, float b, float& 
 // the same on a register pair
 typedef float f2_t __attribute__((ext_vector_type(2)));
 template <int DT> __device__ __forceinline__ f2_t rnT2v(f2_t v) {
-  if constexpr (DT == VC2_F32) {
+  if constexpr (AT<DT> == VC2_F32) {
     return v;
   } else if constexpr (DT == VC2_BF16) {
     typedef __bf16 b2_t __attribute__((ext_vector_type(2)));
@@ -69,17 +85,17 @@ __device__ __forceinline__ f2_t pk_square(f2_t v) {
 
 
 // ---- scalar T load / store -----------------------------------------------------------
-template <int DT> __device__ __forceinline__ float ldT(const void* p, int64_t i) {
-  if constexpr (DT == VC2_F32) {
+template <int DT> __device__ __forceinline__ float ldT(const void* p, int64_t i) {     // (storage)
+  if constexpr (ST<DT> == VC2_F32) {
     return static_cast<const float*>(p)[i];
-  } else if constexpr (DT == VC2_BF16) {
+  } else if constexpr (ST<DT> == VC2_BF16) {
     return __uint_as_float(static_cast<uint32_t>(static_cast<const uint16_t*>(p)[i]) << 16);
   } else {
     return static_cast<float>(static_cast<const _Float16*>(p)[i]);
   }
 }
-template <int DT> __device__ __forceinline__ void stT(void* p, int64_t i, float v) {  // rounds RNE
-  if constexpr (DT == VC2_F32) {
+template <int DT> __device__ __forceinline__ void stT(void* p, int64_t i, float v) {  // rounds RNE (arithmetic: a result)
+  if constexpr (AT<DT> == VC2_F32) {
     static_cast<float*>(p)[i] = v;
   } else if constexpr (DT == VC2_BF16) {
     static_cast<__bf16*>(p)[i] = static_cast<__bf16>(v);
@@ -124,13 +140,15 @@ template <int DT> struct RawVec<DT, 1> { float v; };
 template <> struct RawVec<VC2_F32, 4> { float4 v; };
 template <> struct RawVec<VC2_BF16, 8> { uint4 v; };
 template <> struct RawVec<VC2_F16, 8> { uint4 v; };
+template <> struct RawVec<VC2_BF16_A32, 8> { uint4 v; };
+template <> struct RawVec<VC2_F16_A32, 8> { uint4 v; };
 
 template <int DT, int VEC>
 __device__ __forceinline__ RawVec<DT, VEC> load_raw(const void* __restrict__ x, int64_t elem) {
   RawVec<DT, VEC> r;
   if constexpr (VEC == 1) {
     r.v = ldT<DT>(x, elem);
-  } else if constexpr (DT == VC2_F32) {
+  } else if constexpr (ST<DT> == VC2_F32) {
     r.v = *reinterpret_cast<const float4*>(static_cast<const float*>(x) + elem);
   } else {
     r.v = *reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(x) + elem);
@@ -140,7 +158,7 @@ __device__ __forceinline__ RawVec<DT, VEC> load_raw(const void* __restrict__ x, 
 template <int DT, int VEC> __device__ __forceinline__ RawVec<DT, VEC> zero_raw() {
   RawVec<DT, VEC> r;
   if constexpr (VEC == 1) r.v = 0.f;
-  else if constexpr (DT == VC2_F32) r.v = make_float4(0.f, 0.f, 0.f, 0.f);
+  else if constexpr (ST<DT> == VC2_F32) r.v = make_float4(0.f, 0.f, 0.f, 0.f);
   else r.v = make_uint4(0u, 0u, 0u, 0u);
   return r;
 }
@@ -148,9 +166,9 @@ template <int DT, int VEC>
 __device__ __forceinline__ void unpack(const RawVec<DT, VEC>& r, float (&o)[VEC]) {
   if constexpr (VEC == 1) {
     o[0] = r.v;
-  } else if constexpr (DT == VC2_F32) {
+  } else if constexpr (ST<DT> == VC2_F32) {
     o[0] = r.v.x; o[1] = r.v.y; o[2] = r.v.z; o[3] = r.v.w;
-  } else if constexpr (DT == VC2_BF16) {
+  } else if constexpr (ST<DT> == VC2_BF16) {
     const uint32_t w[4] = {r.v.x, r.v.y, r.v.z, r.v.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) {

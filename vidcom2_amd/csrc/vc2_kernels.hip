@@ -156,7 +156,7 @@ __device__ __forceinline__ void pooled_row(const PoolSrc& ps, int64_t rr, int N,
       if (b[j] > o || b[j] != b[j]) o = b[j];
       if (c[j] > o || c[j] != c[j]) o = c[j];
       if (d[j] > o || d[j] != d[j]) o = d[j];
-    } else if constexpr (DT == VC2_F32) {      // ATen's Vectorized<float> loop (8 channels per step) as GCC contracts it
+    } else if constexpr (AT<DT> == VC2_F32) {      // ATen's Vectorized<float> loop (8 channels per step) as GCC contracts it
       o = w10 * c[j];
       o = __builtin_fmaf(w11, d[j], o); o = __builtin_fmaf(w01, b[j], o); o = __builtin_fmaf(w00, a[j], o);
     } else {                                   // ... and its reduced-precision instantiation (16 channels per step)
@@ -170,9 +170,9 @@ template <int DT, int VEC>
 __device__ __forceinline__ void store_row_T(void* x, int64_t elem, const float (&v)[VEC]) {   // v: T-representable
   if constexpr (VEC == 1) {
     stT<DT>(x, elem, v[0]);
-  } else if constexpr (DT == VC2_F32) {
+  } else if constexpr (ST<DT> == VC2_F32) {
     *reinterpret_cast<float4*>(static_cast<float*>(x) + elem) = make_float4(v[0], v[1], v[2], v[3]);
-  } else if constexpr (DT == VC2_BF16) {
+  } else if constexpr (ST<DT> == VC2_BF16) {
     uint32_t w[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) w[i] = (__float_as_uint(v[2 * i]) >> 16) | (__float_as_uint(v[2 * i + 1]) & 0xFFFF0000u);
@@ -846,20 +846,20 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
 
 template <int DT> __device__ __forceinline__ float lds_elem(const unsigned char* rowbuf, int c) {
-  if constexpr (DT == VC2_F32) return reinterpret_cast<const float*>(rowbuf)[c];
-  else if constexpr (DT == VC2_BF16)
+  if constexpr (ST<DT> == VC2_F32) return reinterpret_cast<const float*>(rowbuf)[c];
+  else if constexpr (ST<DT> == VC2_BF16)
     return __uint_as_float(uint32_t(reinterpret_cast<const uint16_t*>(rowbuf)[c]) << 16);
   else return float(reinterpret_cast<const _Float16*>(rowbuf)[c]);
 }
 
 // the raw bits of one row element in LDS (16-bit types zero-extended), and their fp32 value
 template <int DT> __device__ __forceinline__ uint32_t lds_raw(const unsigned char* rowbuf, int c) {
-  if constexpr (DT == VC2_F32) return reinterpret_cast<const uint32_t*>(rowbuf)[c];
+  if constexpr (ST<DT> == VC2_F32) return reinterpret_cast<const uint32_t*>(rowbuf)[c];
   else return uint32_t(reinterpret_cast<const uint16_t*>(rowbuf)[c]);
 }
 template <int DT> __device__ __forceinline__ float raw_to_f32(uint32_t raw) {
-  if constexpr (DT == VC2_F32) return __uint_as_float(raw);
-  else if constexpr (DT == VC2_BF16) return __uint_as_float(raw << 16);
+  if constexpr (ST<DT> == VC2_F32) return __uint_as_float(raw);
+  else if constexpr (ST<DT> == VC2_BF16) return __uint_as_float(raw << 16);
   else { union { uint16_t u; _Float16 h; } c; c.u = uint16_t(raw); return float(c.h); }
 }
 // two raw row elements in registers
@@ -867,10 +867,10 @@ template <int DT> struct RawPair {
   typedef uint32_t type;
   static __device__ __forceinline__ type make(uint32_t a, uint32_t b) { return a | (b << 16); }
   static __device__ __forceinline__ float lo(type p) {
-    if constexpr (DT == VC2_BF16) return __uint_as_float(p << 16); else return raw_to_f32<DT>(p & 0xFFFFu);
+    if constexpr (ST<DT> == VC2_BF16) return __uint_as_float(p << 16); else return raw_to_f32<DT>(p & 0xFFFFu);
   }
   static __device__ __forceinline__ float hi(type p) {
-    if constexpr (DT == VC2_BF16) return __uint_as_float(p & 0xFFFF0000u); else return raw_to_f32<DT>(p >> 16);
+    if constexpr (ST<DT> == VC2_BF16) return __uint_as_float(p & 0xFFFF0000u); else return raw_to_f32<DT>(p >> 16);
   }
 };
 template <> struct RawPair<VC2_F32> {
@@ -1013,7 +1013,7 @@ constexpr int kFragileUlpsDist = 48;
 __host__ __device__ constexpr int dist_margin_ulps(int, int, int) { return kFragileUlpsDist; }
 
 template <int DT> __device__ __forceinline__ bool near_T_boundary(float y, int margin) {
-  if constexpr (DT == VC2_F32) {
+  if constexpr (AT<DT> == VC2_F32) {
     return false;
   } else {
     constexpr int DROP = (DT == VC2_BF16) ? 16 : 13;            // fp32 mantissa bits the cast drops
@@ -1053,7 +1053,7 @@ template <int DT> __device__ __forceinline__ bool near_T_boundary(float y, int m
 // on to fetch sweep 1's partials for its real A.
 constexpr int kFragileUlpsMean = 16;
 template <int DT> __device__ __forceinline__ bool mean_near_T_boundary(float q) {
-  if constexpr (DT == VC2_F32) {
+  if constexpr (AT<DT> == VC2_F32) {
     return false;
   } else if constexpr (DT == VC2_BF16) {
     return near_T_boundary<DT>(q, kFragileUlpsMean);
@@ -1080,7 +1080,7 @@ __host__ __device__ inline int cascade_depth(int64_t n) {
 inline double margin_depth(int64_t n, int) { return double(cascade_depth(n)); }
 // is a T rounding boundary within `delta` (absolute, >= 0) of q?
 template <int DT> __device__ __forceinline__ bool T_boundary_within(float q, float delta) {
-  if constexpr (DT == VC2_F32) {
+  if constexpr (AT<DT> == VC2_F32) {
     return false;
   } else {
     if (!(delta == delta) || !(fabsf(q) <= 3.0e38f) || delta >= 3.0e38f) return q == q;   // inf / nan bound: replay (NaN means stay)
@@ -1151,7 +1151,7 @@ __device__ float norm_torch_order(const float* sv, int C, int lane) {
     }
     s = __shfl(s, 0, 64);
   } else {                                                      // 8 interleaved FMA chains, then lanes 0..7, then the tail
-    constexpr int CH = (DT == VC2_F32) ? 8 : 16;
+    constexpr int CH = (AT<DT> == VC2_F32) ? 8 : 16;
     const int nv = (C / CH) * CH;
     float acc = 0.f;
     if (lane < 8) {
@@ -1185,10 +1185,10 @@ __device__ float norm_torch_order(const float* sv, int C, int lane) {
 // as fp32, already in sorted order in LDS.
 template <int DT>
 __device__ float sum_torch_order(const float* sq, int C, int lane) {
-  constexpr int CH = (DT == VC2_F32) ? 8 : 16;
+  constexpr int CH = (AT<DT> == VC2_F32) ? 8 : 16;
   const int l = lane & 7, k = (lane >> 3) & 3;
   auto load = [&](int c) -> float {
-    if constexpr (DT == VC2_F32) return sq[CH * c + l];
+    if constexpr (AT<DT> == VC2_F32) return sq[CH * c + l];
     else return sq[CH * c + l] + sq[CH * c + 8 + l];
   };
   const int vec_size = C / CH, size_ilp = vec_size / 4;
@@ -1469,7 +1469,7 @@ __global__ __launch_bounds__(kRowWaves * 64) void k_norm_colsum(const void* __re
         }
         const double t2 = wave_sum_bcast(t);
         nrm32 = float(sqrt(t2));
-        if constexpr (DT == VC2_F32) {
+        if constexpr (AT<DT> == VC2_F32) {
           if (strict && float(t2) == INFINITY) nrm32 = INFINITY;   // (fp32, "torch order": strict is 1, see launch_norm_acc)
         } else {
           ovf = t2 >= kSumSqOverflow;
@@ -2337,7 +2337,7 @@ __global__ __launch_bounds__(64 * kCentreFL) void k_frame_centres(const double* 
   const int g = int(blockIdx.y) - fy;
   const int FGn = int(gridDim.y) - fy;                           // frame groups of this launch
   const int f = g * kCentreFL + fl;
-  const bool replay = strict != 0 && DT != VC2_F32;
+  const bool replay = strict != 0 && AT<DT> != VC2_F32;
   const bool all = strict == 2;
   if (tid == 0) {
     count = 0;
@@ -2639,7 +2639,7 @@ __global__ __launch_bounds__(64) void k_video_centre(const double* __restrict__ 
   struct EndStamp { int i; __device__ ~EndStamp() { if (threadIdx.x == 0 && i < 4096) g_dbg_wg[7][1][i] = wall_clock64(); } } end_stamp_{bx * Y + y};
   if (lane == 0 && bx * Y + y < 4096) g_dbg_wg[7][0][bx * Y + y] = wall_clock64();
 #endif
-  const bool replay = strict != 0 && DT != VC2_F32;
+  const bool replay = strict != 0 && AT<DT> != VC2_F32;
   const bool all = strict == 2;
   const int c = bx * 64 + lane;
   if (bx == 0 && y == 0 && lane == 0) VC2_STAMP(600);
@@ -3010,7 +3010,7 @@ __device__ __forceinline__ float gauss_term(float dist, int a) {
 constexpr int kFragileUlpsExp = 64;
 template <int DT>
 __device__ __forceinline__ bool gauss_term_fast(float dist, int a, float& out) {
-  if constexpr (DT == VC2_F32) {
+  if constexpr (AT<DT> == VC2_F32) {
     out = gauss_term<DT>(dist, a);
     return true;
   } else {
@@ -3044,7 +3044,7 @@ __device__ __forceinline__ float gauss_sum_table(float dist, const MsgAlphas& al
     const float arg = rnT<DT>((-dist) / al.two_a[a]);
     float e = 0.f;
     bool done = false;
-    if constexpr (DT != VC2_F32) {
+    if constexpr (AT<DT> != VC2_F32) {
       const float ef = __builtin_amdgcn_exp2f(arg * 1.44269504088896341f);
       done = fabsf(arg) <= 16.f && !near_T_boundary<DT>(ef, kFragileUlpsExp);
       e = rnT<DT>(ef);
@@ -3401,7 +3401,7 @@ __global__ __launch_bounds__(kRowWaves * 64, 1) void k_dist(const void* __restri
     // a time when 900 other workgroups are streaming rows (in-kernel stamps: 4.1 us of an entry's 5.2 were spent
     // getting the squares into LDS).  The squares go to wave 1's buffer.
     constexpr int kP2 = (NPLB * 64 + kRowWaves * 64 - 1) / (kRowWaves * 64);        // positions per thread
-    const bool dma = DT != VC2_F32 && VEC > 1 && size_t(C) * 4 + 16 <= rowb && C <= NPLB * 64;
+    const bool dma = ST<DT> != VC2_F32 && VEC > 1 && size_t(C) * 4 + 16 <= rowb && C <= NPLB * 64;
     float* sq = reinterpret_cast<float*>(dma ? smem + rowb : smem);
     for (int e = 0; e < cnt; ++e) {
       const int ent = list[e];
@@ -3753,7 +3753,7 @@ __global__ __launch_bounds__(kFrameNT) void k_select(const float* __restrict__ t
   const int extra = map_mode == VC2_MAP_GRID_VID ? grid_h : 0;
   if (tid == 0 && (fl == 0 || fl == FS - 1)) VC2_STAMP(800 + (fl ? 50 : 0));
   if (tid == 0 && fl == 0) VC2_ROUND_RAW(1, 120, 800);
-  if constexpr (DT == VC2_F32) select_frame_load<uint64_t>(smem, total, fl, N);
+  if constexpr (AT<DT> == VC2_F32) select_frame_load<uint64_t>(smem, total, fl, N);
   else select_frame_load<uint32_t>(smem, total, fl, N);
   // ---- budgets of all frames; thread t holds frames t, t + 256, ...
   constexpr int FPT = kFusedScalesMaxF / kFrameNT;
@@ -3895,7 +3895,7 @@ __global__ __launch_bounds__(kFrameNT) void k_select(const float* __restrict__ t
   }
   __shared__ int st_local;
   if (tid == 0) st_local = 0;
-  if constexpr (DT == VC2_F32) select_frame_body<DT, uint64_t>(smem, total, fl, N, k, o0, map_mode, grid_h, stride, cap, idx_out, &st_local);
+  if constexpr (AT<DT> == VC2_F32) select_frame_body<DT, uint64_t>(smem, total, fl, N, k, o0, map_mode, grid_h, stride, cap, idx_out, &st_local);
   else select_frame_body<DT, uint32_t>(smem, total, fl, N, k, o0, map_mode, grid_h, stride, cap, idx_out, &st_local);
   __syncthreads();
   if (tid == 0 && fl == force_guard) st_local = 1;               // (test hook: vc2_selftest_force_guard)
@@ -4409,14 +4409,14 @@ __device__ __forceinline__ uint16_t acc0_f16(uint16_t b) {
   return __builtin_bit_cast(uint16_t, static_cast<_Float16>(0.0f + static_cast<float>(h)));
 }
 template <int DT> __device__ __forceinline__ uint32_t acc0_word(uint32_t w) {
-  if constexpr (DT == VC2_F32) return __float_as_uint(0.0f + __uint_as_float(w));
+  if constexpr (ST<DT> == VC2_F32) return __float_as_uint(0.0f + __uint_as_float(w));
   else if constexpr (DT == VC2_BF16) return acc0_bf16x2(w);
   else return uint32_t(acc0_f16(uint16_t(w & 0xFFFFu))) | (uint32_t(acc0_f16(uint16_t(w >> 16))) << 16);
 }
 // d[de] = 0 + s[se] (s null: zero)
 template <int DT>
 __device__ __forceinline__ void acc0_store_scalar(const unsigned char* s, int64_t se, unsigned char* d, int64_t de) {
-  if constexpr (DT == VC2_F32) {
+  if constexpr (ST<DT> == VC2_F32) {
     reinterpret_cast<float*>(d)[de] = s ? 0.0f + reinterpret_cast<const float*>(s)[se] : 0.0f;
   } else {
     const uint16_t b = s ? reinterpret_cast<const uint16_t*>(s)[se] : uint16_t(0);
@@ -4616,13 +4616,17 @@ inline bool test_seam_on(const char* name) {
   return !e || atoi(e) != 0;
 }
 
-int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total = 0, int block_frames = 0) {
+// dt: a public dtype code; internal_dt (vc2_compress_ex4 only): also the library's storage / arithmetic pairs (vc2_device.h).
+// What follows a row's BYTES (element size, vector width) goes by st_of(dt), what follows the ARITHMETIC (riders, the ORD
+// geometry: the "torch order" replay engine, which fp32 arithmetic does not have) by at_of(dt).
+int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total = 0, int block_frames = 0,
+              bool internal_dt = false) {
   if (F <= 0 || N <= 0 || D <= 0) return fail(VC2_ERR_ARG, "F, N, D must be positive (got %lld, %lld, %lld)",
                                               (long long)F, (long long)N, (long long)D);
-  if (dt < 0 || dt > 2) return fail(VC2_ERR_ARG, "unknown dtype code %d", dt);
+  if (dt < 0 || dt > (internal_dt ? VC2_F16_A32 : 2)) return fail(VC2_ERR_ARG, "unknown dtype code %d", dt);
   p->F = F; p->N = N; p->D = D; p->R = F * N; p->dt = dt;
-  p->ES = dt == VC2_F32 ? 4 : 2;
-  const int full = dt == VC2_F32 ? 4 : 8;
+  p->ES = st_of(dt) == VC2_F32 ? 4 : 2;
+  const int full = st_of(dt) == VC2_F32 ? 4 : 8;
   p->VEC = (D % full == 0) ? full : 1;
   p->CV = int(D / p->VEC);
   if (p->CV > 1024)
@@ -4655,7 +4659,7 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
   // workgroup lives for the whole sweep.  The ORDER riders ("torch order" mode, 16-bit inputs) are workgroups of the
   // same launch, so the splits are chosen to leave them slots -- with 512 + 16 workgroups the last 16 start when the
   // riders end and the sweep takes 51 instead of 36 us; with 384 + 16 it takes 41.
-  const int64_t riders = (cur_mode() && dt != VC2_F32) ? rider_parts_max(p->R, D * p->ES) : 0;
+  const int64_t riders = (cur_mode() && at_of(dt) != VC2_F32) ? rider_parts_max(p->R, D * p->ES) : 0;
   // S is chosen from THIS rank's frames (occupancy), not from the whole video's: the frame sums are fp64 sums of
   // T-rounded x^ in [-1, 1] -- exact (so independent of how the rows are cut) for fp16 by range (2^-24 .. 1, <= 8192
   // rows: 48 bits), and for bf16 unless a nonzero |x^| < 2^-39 meets a frame sum > 2^6
@@ -4674,7 +4678,7 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
     // shapes, every frame workgroup resident next to the riders.  S - 1 workgroups for the first nA frames, S for the
     // others, as many as the slots allow (a workgroup needs at least one block; `part` holds 8 pieces per frame)
     p->ord_S = p->ord_m = p->ord_nA = 0;
-    if (cur_mode() != 0 && dt != VC2_F32 && (D == 1024 || D == 3584 || D == 4096) && N <= 512) {
+    if (cur_mode() != 0 && at_of(dt) != VC2_F32 && (D == 1024 || D == 3584 || D == 4096) && N <= 512) {
       const int64_t nblk = std::max<int64_t>(1, N / 16);
       const int64_t smax = std::min<int64_t>(8, nblk), slots = 512 - riders;
       const int64_t s_lo = std::min<int64_t>(smax, slots / F);
@@ -4787,6 +4791,18 @@ struct ProfScope {
 #define VC2_DISPATCH_VEC(p, ...)                                            \
   VC2_DISPATCH_DT((p).dt, if ((p).VEC == 1) { constexpr int VEC = 1; __VA_ARGS__; } \
                   else { constexpr int VEC = Tr<DT>::VEC; __VA_ARGS__; })
+// ... and the same with the two internal storage / arithmetic pairs: ONLY for the launches of the fused pass that read rows
+// and round results (the variance reduction, sweeps 2 and 3, the two centre kernels).  Every other launch keeps three dtypes:
+// a kernel that only reads rows takes st_of(dt), one that only rounds takes at_of(dt).
+#define VC2_DISPATCH_DT_PASS(dt, ...)                                               \
+  switch (dt) {                                                                     \
+    case VC2_BF16_A32: { constexpr int DT = VC2_BF16_A32; __VA_ARGS__; } break;     \
+    case VC2_F16_A32: { constexpr int DT = VC2_F16_A32; __VA_ARGS__; } break;       \
+    default: VC2_DISPATCH_DT(dt, __VA_ARGS__)                                       \
+  }
+#define VC2_DISPATCH_VEC_PASS(p, ...)                                       \
+  VC2_DISPATCH_DT_PASS((p).dt, if ((p).VEC == 1) { constexpr int VEC = 1; __VA_ARGS__; } \
+                       else { constexpr int VEC = Tr<DT>::VEC; __VA_ARGS__; })
 
 int need_ws(const Plan& p, void* ws, size_t ws_bytes) {
   if (!ws) return fail(VC2_ERR_ARG, "workspace pointer is null");
@@ -4804,12 +4820,15 @@ int launch_stats_sweep(const Plan& p, const void* x, void* ws, const PoolSrc& po
   if (p.G > 65535) return fail(VC2_ERR_UNSUPPORTED, "too many sweep-1 row groups (%d)", p.G);
   dim3 grid(unsigned(cdiv(p.CV, p.stat_lanes)), unsigned(p.G));
   ProfScope ps_(KID_STATS, st);
+  // (the sweep sums raw values in fp64: it is arithmetic-neutral, so a storage / arithmetic pair runs its storage dtype's kernel)
+  Plan ps = p;
+  ps.dt = st_of(p.dt);
   if (pool.xin) {
-    VC2_DISPATCH_VEC(p, hipLaunchKernelGGL((k_chan_stats<DT, VEC, 8, 1>), grid, dim3(kStatsWaves * 64), 0, st, x,
+    VC2_DISPATCH_VEC(ps, hipLaunchKernelGGL((k_chan_stats<DT, VEC, 8, 1>), grid, dim3(kStatsWaves * 64), 0, st, x,
                                             p.R, int(p.D), p.CV, int(p.N), p.stat_splits, p.rows_per_group, p.BF, part,
                                             pool, nullptr, p.stat_lanes));
   } else {
-    VC2_DISPATCH_VEC(p, hipLaunchKernelGGL((k_chan_stats<DT, VEC, 8, 0>), grid, dim3(kStatsWaves * 64), 0, st, x,
+    VC2_DISPATCH_VEC(ps, hipLaunchKernelGGL((k_chan_stats<DT, VEC, 8, 0>), grid, dim3(kStatsWaves * 64), 0, st, x,
                                             p.R, int(p.D), p.CV, int(p.N), p.stat_splits, p.rows_per_group, p.BF, part,
                                             pool, var_reset, p.stat_lanes));
   }
@@ -4831,7 +4850,7 @@ int launch_chan_stats(const Plan& p, const void* x, void* ws, double* bstats, vo
     // narrow column slabs (16 columns x 16 lanes: 224 workgroups at D = 3584) spread the loads of sweep 1's partials
     // (7 MB) over the whole chip instead of 56 CUs
     constexpr int CW = 16;
-    VC2_DISPATCH_DT(p.dt, hipLaunchKernelGGL((k_var_from_stats<DT, CW>), dim3(unsigned(cdiv(p.D, CW))), dim3(CW * kRedGL), 0, st,
+    VC2_DISPATCH_DT_PASS(p.dt, hipLaunchKernelGGL((k_var_from_stats<DT, CW>), dim3(unsigned(cdiv(p.D, CW))), dim3(CW * kRedGL), 0, st,
                          (const double*)nullptr, p.NB, n_each, n_last, int(p.D), var_T, var_f32,
                          zero_queue_counters ? wsp<int>(ws, p.o_ticket) : (int*)nullptr, src,
                          make_fold_tab(p.NB, n_each, n_last),
@@ -4899,13 +4918,13 @@ struct ChanSet {
 };
 inline ChanSet make_chanset(const Plan& p, const int* cols, const int* spos, int64_t C) {
   ChanSet cs{cols, spos, int(C), 0};
-  cs.strict = (cur_mode() && p.ES == 2 && (cols == nullptr || spos)) ? cur_mode() : 0;   // 2 = replay always
+  cs.strict = (cur_mode() && at_of(p.dt) != VC2_F32 && (cols == nullptr || spos)) ? cur_mode() : 0;   // 2 = replay always
   return cs;
 }
 
 // ACC policy of the two scoring sweeps: fp32 accumulation + wider replay margins in "torch order" mode (half
 // precision only), fp64 otherwise
-inline bool fast_acc(const Plan& p, const ChanSet& cs) { return cs.strict != 0 && p.dt != VC2_F32; }
+inline bool fast_acc(const Plan& p, const ChanSet& cs) { return cs.strict != 0 && at_of(p.dt) != VC2_F32; }
 
 template <int DT, int VEC, int NPLB, int ACC>
 int launch_norm_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, const OrderArgs& rider, hipStream_t st) {
@@ -4920,14 +4939,14 @@ int launch_norm_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, c
   // (fp32 has no replays -- cs.strict is 0 -- but "torch order" mode tells the sweep to overflow where torch does: 1)
   hipLaunchKernelGGL((k_norm_colsum<DT, VEC, NPLB, ACC, RIDER>), dim3(unsigned(p.S_W + (rider.perm ? (rider.parts & 0xFF) : 0))),
                      dim3(kRowWaves * 64), smem, st, x,
-                     int(p.N), int(p.D), p.CV, C, cols, p.dt == VC2_F32 ? (cur_mode() ? 1 : 0) : cs.strict, p.S, p.S_q, p.R,
+                     int(p.N), int(p.D), p.CV, C, cols, at_of(p.dt) == VC2_F32 ? (cur_mode() ? 1 : 0) : cs.strict, p.S, p.S_q, p.R,
                      wsp<float>(ws, p.o_den), wsp<double>(ws, p.o_part_col), wsp<int>(ws, p.o_ticket),
                      wsp<unsigned long long>(ws, p.o_nfixlist), int(p.R), wsp<uint8_t>(ws, p.o_rflag), rider);
   return VC2_OK;
 }
 // the streamlined sweep 2 (k_norm_colsum2): 16-bit rows of NCH full 1 KiB chunks, C = D / 2, "torch order" mode
 inline int s2v2_nch(const Plan& p, const ChanSet& cs) {
-  if (p.dt == VC2_F32 || p.VEC == 1 || !cs.cols || !fast_acc(p, cs)) return 0;
+  if (at_of(p.dt) == VC2_F32 || p.VEC == 1 || !cs.cols || !fast_acc(p, cs)) return 0;
   if (p.D % 512 != 0 || int64_t(cs.C) * 2 != p.D || p.R >= (int64_t(1) << 31) || p.F * int64_t(p.S) >= (int64_t(1) << 31) / 8) return 0;
   const int nch = int(p.D / 512);
   return (nch == 2 || nch == 7 || nch == 8) ? nch : 0;
@@ -4964,7 +4983,7 @@ int launch_norm_v2(const Plan& p, const void* x, const ChanSet& cs, void* ws, co
 }
 template <int DT, int VEC, int NPLB>
 int launch_norm_t(const Plan& p, const void* x, const ChanSet& cs, void* ws, const OrderArgs& rider, hipStream_t st) {
-  if constexpr (DT != VC2_F32 && VEC > 1) {
+  if constexpr (AT<DT> != VC2_F32 && VEC > 1) {
     switch (s2v2_nch(p, cs)) {
       case 2: if constexpr (NPLB == 8) return launch_norm_v2<DT, 2>(p, x, cs, ws, rider, st); break;
       case 7: if constexpr (NPLB == 28) return launch_norm_v2<DT, 7>(p, x, cs, ws, rider, st); break;
@@ -4972,7 +4991,7 @@ int launch_norm_t(const Plan& p, const void* x, const ChanSet& cs, void* ws, con
       default: break;
     }
   }
-  if constexpr (DT != VC2_F32) {
+  if constexpr (AT<DT> != VC2_F32) {
     if (fast_acc(p, cs)) return launch_norm_acc<DT, VEC, NPLB, 1>(p, x, cs, ws, rider, st);
   }
   return launch_norm_acc<DT, VEC, NPLB, 0>(p, x, cs, ws, rider, st);
@@ -5024,7 +5043,7 @@ int launch_dist_acc(const Plan& p, const void* x, const ChanSet& cs, void* ws, c
 template <int DT, int VEC, int NPLB>
 int launch_dist_t(const Plan& p, const void* x, const ChanSet& cs, void* ws, const DistOut& o, hipStream_t st,
                   const MsgAlphas* al) {
-  if constexpr (DT != VC2_F32) {
+  if constexpr (AT<DT> != VC2_F32) {
     if (fast_acc(p, cs)) return launch_dist_acc<DT, VEC, NPLB, 1>(p, x, cs, ws, o, st, al);
   }
   return launch_dist_acc<DT, VEC, NPLB, 0>(p, x, cs, ws, o, st, al);
@@ -5060,13 +5079,13 @@ int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, boo
   if (ride.perm) ride.parts = order_parts(ride.k, rider_parts_max(p.R, p.D * p.ES));
   { ProfScope ps_(KID_NORM_COLSUM, st);
   int rc = VC2_OK;
-  VC2_DISPATCH_VEC(p, rc = VC2_DISPATCH_NPL(npl, launch_norm_t, p, x, cs, ws, ride, st));
+  VC2_DISPATCH_VEC_PASS(p, rc = VC2_DISPATCH_NPL(npl, launch_norm_t, p, x, cs, ws, ride, st));
   if (rc) return rc; }
   // Fused centre launch (see k_frame_centres): the norm fix-ups as rider workgroups -- single rank (the corrections of the
   // video-centre sums are added by k_video_centre), 16-bit inputs on the vector path, <= 32 compact positions per lane
   // (the rider's registers must fit a 1024-thread workgroup), frames short enough for the replays; else, and for
   // per-kernel timing, k_norm_fix runs first and k_frame_centres applies its corrections itself.
-  const bool replays = cs.strict != 0 && p.dt != VC2_F32;
+  const bool replays = cs.strict != 0 && at_of(p.dt) != VC2_F32;
   const int rcap = int(std::min<int64_t>(p.F * int64_t(C), INT32_MAX / 2));      // regular entries: every mean at most once
   const int rcap2 = int(p.F * cdiv(C, 64));                                        // correction entries: every (frame, column block) once
   const bool fused = replays && single_rank && !g_prof && p.VEC > 1 && npl <= 32 && (((p.N >> 4) + 15) >> 4) <= kCFixSolo &&
@@ -5106,7 +5125,7 @@ int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, boo
                        OrdSrc{ord ? wsp<float>(ws, p.o_bsum) : (const float*)nullptr, ord ? 1 : 0, ord ? p.ord_nA : 0});
   };
   if (!fused) {
-    VC2_DISPATCH_DT(p.dt, launch_fc(k_frame_centres<DT, 1, 0>));
+    VC2_DISPATCH_DT_PASS(p.dt, launch_fc(k_frame_centres<DT, 1, 0>));
   } else if (p.dt == VC2_BF16) {
     constexpr int DT = VC2_BF16, VEC = Tr<VC2_BF16>::VEC;
     if (npl <= 8) launch_fc(k_frame_centres<DT, VEC, 8>); else if (npl <= 16) launch_fc(k_frame_centres<DT, VEC, 16>);
@@ -5136,7 +5155,7 @@ int launch_phase1(const Plan& p, const void* x, const ChanSet& cs, void* ws, boo
     const int G1v = int(cdiv(p.R >> lpv, int64_t(1) << lpv));
     const int Y = int(std::max<int64_t>(1, std::min<int64_t>(32, cdiv(G1v, 64 >> std::min(lpv, 6)))));
     const int RY = replays ? int(cdiv(rwaves, cdiv(C, 64))) : 0;
-    VC2_DISPATCH_DT(p.dt, hipLaunchKernelGGL((k_video_centre<DT>), dim3(unsigned(cdiv(C, 64)), unsigned(Y + RY)), dim3(64),
+    VC2_DISPATCH_DT_PASS(p.dt, hipLaunchKernelGGL((k_video_centre<DT>), dim3(unsigned(cdiv(C, 64)), unsigned(Y + RY)), dim3(64),
                                              vc_lds_bytes(p.R, p.N), st, cpart, FG, int64_t(C), C, p.R, wsp<float>(ws, p.o_vc), x, int(p.D),
                                              cs.cols, cs.spos, wsp<float>(ws, p.o_den), cs.strict, 1,
                                              wsp<int>(ws, p.o_ticket) + kTkVcFragile,
@@ -5170,11 +5189,12 @@ int launch_phase2(const Plan& p, const void* x, const ChanSet& cs, void* ws, voi
   { int rc = VC2_OK;
   const int npl = int(cdiv(C, 64));
   const DistOut o{v_T, f_T, total};
-  VC2_DISPATCH_VEC(p, rc = VC2_DISPATCH_NPL(npl, launch_dist_t, p, x, cs, ws, o, st, al));
+  VC2_DISPATCH_VEC_PASS(p, rc = VC2_DISPATCH_NPL(npl, launch_dist_t, p, x, cs, ws, o, st, al));
   if (rc) return rc; }
   if (s) {
     ProfScope ps_(KID_EPILOGUE, st);
-    VC2_DISPATCH_DT(p.dt, hipLaunchKernelGGL((k_frame_scores<DT>), dim3(unsigned(cdiv(p.F, 128))), dim3(128), 0, st,
+    // (rounds, reads no row: the arithmetic dtype's kernel)
+    VC2_DISPATCH_DT(at_of(p.dt), hipLaunchKernelGGL((k_frame_scores<DT>), dim3(unsigned(cdiv(p.F, 128))), dim3(128), 0, st,
                                              wsp<double>(ws, p.o_vpart), int(p.F), p.S2, int(p.N), s));
   }
   return check_launch("scores phase 2");
@@ -5384,7 +5404,7 @@ int vc2_scores_phase1(const void* x, int64_t F, int64_t N, int64_t D, int dtype,
 static bool vc_blocks_ok(const Plan& p, int64_t R_total, int strict) {
   const int64_t B = int64_t(1) << cascade_lp(R_total);      // (a level-0 block meets at most two ranks)
   (void)B;                                                    // (a block may meet any number of ranks: k_vc_finish)
-  return strict != 0 && p.dt != VC2_F32 && R_total % p.R == 0 && cascade_modelled(R_total);
+  return strict != 0 && at_of(p.dt) != VC2_F32 && R_total % p.R == 0 && cascade_modelled(R_total);
 }
 
 int vc2_video_centre_blocks(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
@@ -5521,7 +5541,7 @@ int vc2_scores_phase2_blocks(const void* x, int64_t F, int64_t N, int64_t D, int
 // array; from it this rank's row0 (prefix sum), the record stride all ranks share (the largest rank's) and the prefix
 // table k_vc_finish_ragged takes by value.  The flag / sweep launches are the equal-rank entry points' own.
 static bool vc_blocks_ok_ragged(const Plan& p, int64_t R_total, int strict) {
-  return strict != 0 && p.dt != VC2_F32 && cascade_modelled(R_total);
+  return strict != 0 && at_of(p.dt) != VC2_F32 && cascade_modelled(R_total);
 }
 static int make_rank_table(const int64_t* rank_rows, int world, int rank, int64_t F, int64_t N, int64_t R_total,
                            VcRankTable* tab) {
@@ -5944,7 +5964,23 @@ int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
                      void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
                      const void* tail, int64_t tail_rows, int flags, int64_t* K_host, const vc2_pass_params* params,
                      void* stream) {
+  return vc2_compress_ex4(x, F, N, D, dtype, base_scale, map_mode, grid_h, gather_src, gather_rows, ws, ws_bytes, out_rows,
+                          idx_out, cap, ks, K_out, v_T, f_T, tail, tail_rows, flags, K_host, params, dtype, stream);
+}
+
+int vc2_compress_ex4(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale, int map_mode,
+                     int64_t grid_h, const void* gather_src, int64_t gather_rows, void* ws, size_t ws_bytes,
+                     void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
+                     const void* tail, int64_t tail_rows, int flags, int64_t* K_host, const vc2_pass_params* params,
+                     int score_dtype, void* stream) {
   if (!x || !idx_out || !ks || !K_out) return fail(VC2_ERR_ARG, "null pointer");
+  // score_dtype == dtype: the pass of vc2_compress_ex3, the same launches.  VC2_F32 over 16-bit rows: the library's storage /
+  // arithmetic pair (vc2_device.h) -- 16-bit loads, the arithmetic (and the launches) of the fp32-input pass.
+  if (dtype < VC2_F32 || dtype > VC2_F16) return fail(VC2_ERR_ARG, "unknown dtype code %d", dtype);
+  if (score_dtype != dtype && !(score_dtype == VC2_F32 && (dtype == VC2_BF16 || dtype == VC2_F16)))
+    return fail(VC2_ERR_ARG, "score_dtype %d with dtype %d: it must equal dtype, or be VC2_F32 over 16-bit rows", score_dtype, dtype);
+  const int pdt = score_dtype == dtype ? dtype : (dtype == VC2_BF16 ? VC2_BF16_A32 : VC2_F16_A32);
+  const int adt = at_of(pdt);                             // the kernels that round and read no row take this dtype
   // the pass's hyper-parameters: checked before anything else so that nothing is enqueued on a bad set.  A set equal to the
   // reference's is the default pass: the same kernel instantiations as params == NULL.
   int64_t kc = int64_t(double(D) * 0.5);                  // int(x.shape[-1] * ratio), vidcom2.py:41
@@ -5977,7 +6013,7 @@ int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   if (map_mode == VC2_MAP_GRID_VID && (grid_h <= 0 || grid_h * grid_h != N))
     return fail(VC2_ERR_ARG, "grid_vid mapping needs N == grid_h^2");
   Plan p;
-  int rc = make_plan(F, N, D, dtype, &p);
+  int rc = make_plan(F, N, D, pdt, &p, 0, 0, /*internal_dt=*/true);
   if (rc) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
   if (D > 8192) return fail(VC2_ERR_UNSUPPORTED, "D=%lld > 8192 channels", (long long)D);
@@ -5998,7 +6034,7 @@ int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   }
   float* var_f32 = wsp<float>(ws, p.o_var_f32);
   int* cols = wsp<int>(ws, p.o_cols);
-  const bool strict = cur_mode() && p.ES == 2;
+  const bool strict = cur_mode() && adt != VC2_F32;          // (the replay engine: 16-bit ARITHMETIC only)
   int* spos = strict ? wsp<int>(ws, p.o_spos) : nullptr;
   int* perm = strict ? wsp<int>(ws, p.o_perm) : nullptr;
   // (wperm / wcpos live in the o_tmp_f32 scratch, free until the selection stage: 2 * kc words <= R or D floats)
@@ -6013,7 +6049,8 @@ int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   static const int n_cus = [] { int dev = 0, n = 0; (void)hipGetDevice(&dev);
                                 if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) { (void)hipGetLastError(); n = 0; }
                                 return n; }();
-  if (test_seam_on("VC2_VARSEL") && n_cus >= 16 && test_seam_on("VC2_SEL4") && p.ES == 2 && D <= 4096 && !(flags & VC2_FLAG_HAVE_STATS) && !g_prof && kc > 0 && kc < D) {
+  // (16-bit ARITHMETIC: fp32 variances need the 64-bit selection words of k_chan_select, as fp32 inputs do)
+  if (test_seam_on("VC2_VARSEL") && n_cus >= 16 && test_seam_on("VC2_SEL4") && adt != VC2_F32 && D <= 4096 && !(flags & VC2_FLAG_HAVE_STATS) && !g_prof && kc > 0 && kc < D) {
     if ((rc = launch_stats_sweep(p, x, ws, PoolSrc{}, st, reinterpret_cast<uint32_t*>(var_f32)))) return rc;
     const int64_t n_each = int64_t(p.BF) * p.N, n_last = p.R - int64_t(p.NB - 1) * n_each;
     VarSelArgs va{p.NB, n_each, n_last, int(D), var_f32, wsp<int>(ws, p.o_ticket),
@@ -6035,7 +6072,7 @@ int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
     if ((rc = launch_chan_stats(p, x, ws, nullptr, nullptr, var_f32, st, /*zero_queue_counters=*/true,
                                 /*have_partials=*/(flags & VC2_FLAG_HAVE_STATS) != 0, /*kstatus=*/K_out + 1)))
       return rc;
-    if ((rc = launch_chan_select(var_f32, D, kc, nullptr, cols, perm, st, wperm, wcpos, status, /*words64_expected=*/p.ES == 4))) return rc;
+    if ((rc = launch_chan_select(var_f32, D, kc, nullptr, cols, perm, st, wperm, wcpos, status, /*words64_expected=*/adt == VC2_F32))) return rc;
   }
   const ChanSet cs = make_chanset(p, cols, spos, kc);
   // torch.topk's ORDER of the selected channels (needed only by the "torch order" fix-ups, which run after sweep 2)
@@ -6054,13 +6091,13 @@ int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   float* s = fused_budget ? nullptr : wsp<float>(ws, p.o_s);
   if ((rc = launch_phase2(p, x, cs, ws, v_T, f_T, total, s, st, al))) return rc;
   if (fused_budget) {
-    rc = launch_select(dtype, total, F, 0, F, N, map_mode, grid_h, ks, wsp<int64_t>(ws, p.o_offs), idx_out, cap, K_out,
+    rc = launch_select(adt, total, F, 0, F, N, map_mode, grid_h, ks, wsp<int64_t>(ws, p.o_offs), idx_out, cap, K_out,
                        BudgetSrc{nullptr, wsp<double>(ws, p.o_vpart), p.S2, nullptr, bs, temp, scales, 0,
                                  wsp<int>(ws, p.o_ticket) + kTkStatus, reinterpret_cast<long long*>(K_host),
                                  wsp<int>(ws, p.o_ticket) + kTkSelArrive}, st);
   } else {
-    if ((rc = launch_scales(dtype, s, F, bs, temp, wsp<float>(ws, p.o_zbuf), scales, nullptr, st))) return rc;
-    rc = launch_select(dtype, total, F, 0, F, N, map_mode, grid_h, ks, wsp<int64_t>(ws, p.o_offs), idx_out, cap, K_out,
+    if ((rc = launch_scales(adt, s, F, bs, temp, wsp<float>(ws, p.o_zbuf), scales, nullptr, st))) return rc;
+    rc = launch_select(adt, total, F, 0, F, N, map_mode, grid_h, ks, wsp<int64_t>(ws, p.o_offs), idx_out, cap, K_out,
                        BudgetSrc{scales, nullptr, 0, nullptr, bs, temp, nullptr, 0, wsp<int>(ws, p.o_ticket) + kTkStatus,
                                  reinterpret_cast<long long*>(K_host), wsp<int>(ws, p.o_ticket) + kTkSelArrive}, st);
   }

@@ -97,11 +97,30 @@ def pass_params():
     return PassParams(**kw)
 
 
+def score_dtype():
+    """`VC2_SCORE_DTYPE=fp32`, read at call time: the hooks' passes score bf16 / fp16 features in fp32 (the reference applied
+    to the widened features, `compress(..., score_dtype=torch.float32)`; a no-op for fp32 features).  None when unset;
+    any other value raises ValueError naming the knob."""
+    raw = os.getenv("VC2_SCORE_DTYPE")
+    if raw is None:
+        return None
+    if raw != "fp32":
+        raise ValueError(f"VC2_SCORE_DTYPE={raw!r}: the only value is 'fp32' (unset: score in the features' dtype)")
+    import torch
+    return torch.float32
+
+
 def params_kwargs() -> dict:
-    """`{"params": pass_params()}` for the hooks' calls into the pass; empty when no knob is set, so that the call is
-    exactly the one without params."""
+    """The knobs' keyword arguments for the hooks' calls into the pass -- `params` (pass_params()) and `score_dtype`
+    (score_dtype()) --, each only when its knobs are set: with none set the call is exactly the one without them."""
+    kw = {}
     p = pass_params()
-    return {} if p is None else {"params": p}
+    if p is not None:
+        kw["params"] = p
+    sd = score_dtype()
+    if sd is not None:
+        kw["score_dtype"] = sd
+    return kw
 
 
 def compressor_enabled() -> bool:

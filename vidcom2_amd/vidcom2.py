@@ -135,6 +135,17 @@ def _c_params(params: Optional["PassParams"], D: int) -> Optional[_CPassParams]:
     return _CPassParams(C, params.temp, len(params.alphas), (ctypes.c_double * _MAX_ALPHAS)(*params.alphas))
 
 
+def _norm_score_dtype(score_dtype, dtype) -> Optional[torch.dtype]:
+    """None for "score in the input's dtype" (score_dtype None or equal to it: the plain call, its kernels and its cached
+    plans); torch.float32 over a bf16 / fp16 tensor: the fp32-scored pass (vc2_compress_ex4)."""
+    if score_dtype is None or score_dtype == dtype:
+        return None
+    if score_dtype == torch.float32 and dtype in (torch.bfloat16, torch.float16):
+        return torch.float32
+    raise ValueError(f"score_dtype must be None, the input's dtype ({dtype}) or torch.float32 over a bfloat16 / float16 "
+                     f"tensor, got {score_dtype!r}")
+
+
 def _first_tensor(a):
     if isinstance(a, torch.Tensor):
         return a
@@ -235,10 +246,14 @@ class CompressPlan:
 
     def __init__(self, F: int, N: int, D: int, dtype, device, base_scale: float = 0.25,
                  mapper: str = "linear", grid_h: int = 0, want_scores: bool = False, gather: bool = True,
-                 tail_rows: int = 0, ws: Optional[torch.Tensor] = None, params: Optional[PassParams] = None):
+                 tail_rows: int = 0, ws: Optional[torch.Tensor] = None, score_dtype: Optional[torch.dtype] = None,
+                 params: Optional[PassParams] = None):
         if mapper not in ("linear", "grid_vid"):
             raise ValueError(f"unknown mapper {mapper!r}")
         self.F, self.N, self.D, self.dtype, self.device = int(F), int(N), int(D), dtype, torch.device(device)
+        # the dtype the pass rounds in: the input's, or fp32 over 16-bit rows (the reference on x.float(), no fp32 copy)
+        self.score_dtype = _norm_score_dtype(score_dtype, dtype)
+        self.arith_dtype = dtype if self.score_dtype is None else self.score_dtype
         self.params = _norm_params(params)               # None: the reference's hyper-parameters
         self._cparams = _c_params(self.params, self.D)
         self.base_scale = float(base_scale)
@@ -249,7 +264,7 @@ class CompressPlan:
         if self.map_mode == MAP_GRID_VID:
             cap += self.F * self.grid_h
         self.cap = cap
-        if dtype != torch.float32 and _ffi.get_mode() == "torch" and not cascade_modelled(self.F * self.N):
+        if self.arith_dtype != torch.float32 and _ffi.get_mode() == "torch" and not cascade_modelled(self.F * self.N):
             # beyond this size the centre-mean replays do not model torch's outer-sum cascade (SumKernel.cpp level_power
             # 4 / 5 / 6 are modelled, i.e. up to 2^25 tokens per video): say so instead of silently keeping the exactly
             # rounded means
@@ -281,11 +296,12 @@ class CompressPlan:
     def _alloc_outputs(self, n: Optional[int] = None) -> OutputSet:
         """A fresh output set; with n: n sets in ONE allocation per output kind ([n, ...] tensors: compress_batch)."""
         dt, dev, lead = self.dtype, self.device, () if n is None else (n,)     # (sizes as arguments: ~1 us less each)
+        sdt = self.arith_dtype                                                 # (scores: the dtype the pass rounds in)
         return OutputSet(torch.empty(*lead, self.cap, dtype=torch.int64, device=dev),
                          torch.empty(*lead, self.F, dtype=torch.int64, device=dev),
                          torch.empty(*lead, self.cap + self.tail_rows, self.D, dtype=dt, device=dev) if self._gather else None,
-                         torch.empty(*lead, self.F, self.N, dtype=dt, device=dev) if self._want_scores else None,
-                         torch.empty(*lead, self.F, self.N, dtype=dt, device=dev) if self._want_scores else None,
+                         torch.empty(*lead, self.F, self.N, dtype=sdt, device=dev) if self._want_scores else None,
+                         torch.empty(*lead, self.F, self.N, dtype=sdt, device=dev) if self._want_scores else None,
                          torch.empty(*lead, 2, dtype=torch.int64, device=dev))
 
     def new_outputs(self) -> None:
@@ -303,7 +319,7 @@ class CompressPlan:
         if self._gather:
             n += (self.cap + self.tail_rows) * self.D * es
         if self._want_scores:
-            n += 2 * self.F * self.N * es
+            n += 2 * self.F * self.N * torch.empty(0, dtype=self.arith_dtype).element_size()
         return n
 
     def cached_bytes(self) -> int:
@@ -350,14 +366,14 @@ class CompressPlan:
             khost = kh.addr
         self._armed = st if mirror else None
         with on_device(self.device):
-            rc = lib().vc2_compress_ex3(ptr(flat), self.F, self.N, self.D, DTYPE_CODE[self.dtype], self.base_scale,
+            rc = lib().vc2_compress_ex4(ptr(flat), self.F, self.N, self.D, DTYPE_CODE[self.dtype], self.base_scale,
                                         self.map_mode, self.grid_h, ptr(src if o.rows is not None else None),
                                         src.shape[0], ptr(self.ws), self.ws.numel(), ptr(o.rows), ptr(o.idx),
                                         self.cap, ptr(o.ks), ptr(o.kout), ptr(o.v), ptr(o.f),
                                         ptr(tail if self.tail_rows else None), self.tail_rows,
                                         1 if have_stats else 0, khost,
                                         None if self._cparams is None else ctypes.addressof(self._cparams),
-                                        ctypes.c_void_p(st.cuda_stream))
+                                        DTYPE_CODE[self.arith_dtype], ctypes.c_void_p(st.cuda_stream))
         if rc != 0 and mirror:                           # (nothing was launched: the mirror block is not in flight)
             self._khost.in_flight = False
             self._armed = None
@@ -446,13 +462,15 @@ _PREALLOC = os.environ.get("VC2_PREALLOC", "1") != "0"             # next call's
 
 
 def _cached_plan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores, gather, tail_rows,
-                 fresh_outputs: bool = False, params: Optional[PassParams] = None) -> "CompressPlan":
+                 fresh_outputs: bool = False, params: Optional[PassParams] = None,
+                 score_dtype: Optional[torch.dtype] = None) -> "CompressPlan":
     device = torch.device(device)
     params = _norm_params(params)
+    score_dtype = _norm_score_dtype(score_dtype, dtype)      # (None / the input's dtype: the plain call's key and plan)
     if device.index is None:
         device = torch.device(device.type, torch.cuda.current_device())
     key = (F, N, D, dtype, device, float(base_scale), mapper, int(grid_h), bool(want_scores), bool(gather),
-           int(tail_rows), torch.cuda.current_stream(device).cuda_stream, threading.get_ident(), _ffi.get_mode(), params)
+           int(tail_rows), torch.cuda.current_stream(device).cuda_stream, threading.get_ident(), _ffi.get_mode(), params, score_dtype)
     # (the key holds the thread id, so a plan is only ever USED by one thread; the dictionary itself is shared: another
     #  thread's eviction between get and move_to_end raised KeyError before the lock)
     with _PLAN_LOCK:
@@ -461,7 +479,7 @@ def _cached_plan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores
             _PLAN_CACHE.move_to_end(key)
     if plan is None:
         plan = CompressPlan(F, N, D, dtype, device, base_scale, mapper, grid_h, want_scores, gather, tail_rows,
-                            params=params)
+                            params=params, score_dtype=score_dtype)
         if _PLAN_CACHE_MAX > 0:
             with _PLAN_LOCK:
                 _PLAN_CACHE[key] = plan
@@ -571,8 +589,13 @@ def _raise_status(status: int, cap: int, K: int) -> None:
 def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, mapper: str = "linear",
              grid_h: int = 0, img_feat: Optional[torch.Tensor] = None, want_scores: bool = False,
              gather: bool = True, tail: Optional[torch.Tensor] = None,
-             stats_ws: Optional[torch.Tensor] = None, params: Optional[PassParams] = None) -> CompressionResult:
+             stats_ws: Optional[torch.Tensor] = None, score_dtype: Optional[torch.dtype] = None,
+             params: Optional[PassParams] = None) -> CompressionResult:
     """One whole pass: feature tensor resident in HBM -> kept rows + indices + budgets.
+    score_dtype: the dtype the pass scores in.  None or the input's dtype: the reference's behaviour (every op rounds to the
+    input dtype).  torch.float32 over a bf16 / fp16 tensor: the reference applied to `flattened_feat.float()` -- the kept set
+    a user gets today from `compress(x.float(), ...)` -- from the 16-bit tensor itself: no fp32 copy, half the bytes, rows
+    gathered in the input dtype; `v_score` / `f_score` are then fp32 and `_ffi.set_mode` changes nothing, as for fp32 inputs.
     params: channel ratio, softmax temperature and Gaussian scales other than the reference's (PassParams); None, or a
     PassParams equal to the defaults: the reference's.
     tail ([m, D], e.g. LLaVA's newline embedding): written behind the kept rows by the gather launch itself;
@@ -583,6 +606,7 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     indices, budgets and scores are not."""
     params = _norm_params(params)
     x = _prep(flattened_feat, "flattened_feat")
+    score_dtype = _norm_score_dtype(score_dtype, x.dtype)
     if x.dim() != 2:
         raise RuntimeError(f"flattened_feat must be 2-D [frames*tokens, dim], got {tuple(x.shape)}")
     R, D = x.shape
@@ -615,15 +639,15 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     ntail = 0 if tail is None else tail.shape[0]
     if stats_ws is not None:          # (the statistics live in the caller's workspace: a plan around it, not cached)
         plan = CompressPlan(R // tpf, tpf, D, x.dtype, x.device, base_scale, mapper, grid_h, want_scores, gather,
-                            tail_rows=ntail, ws=stats_ws, params=params)
+                            tail_rows=ntail, ws=stats_ws, params=params, score_dtype=score_dtype)
     else:
         plan = _cached_plan(R // tpf, tpf, D, x.dtype, x.device, base_scale, mapper, grid_h, want_scores, gather, ntail,
-                            fresh_outputs=True, params=params)
+                            fresh_outputs=True, params=params, score_dtype=score_dtype)
     plan.enqueue(x, src, tail, have_stats=stats_ws is not None, mirror=_EARLY_COUNT)
     if stats_ws is None and _PREALLOC and _PLAN_CACHE_MAX > 0 and plan.output_bytes() <= _SPARE_MAX_BYTES:
         plan.prepare_spare()              # (the GPU is busy for the next ~190 us: the next call's outputs cost nothing here)
     res = plan.finish()
-    _check_budgets(res.ks, tpf, x.dtype)
+    _check_budgets(res.ks, tpf, plan.arith_dtype)        # (RN_T(scale * N) rounds in the dtype the pass scores in)
     gsrc = img_feat if mapper == "grid_vid" else flattened_feat
     if gather and _ag.wants_grad(gsrc, tail_user):
         res.rows = _ag.attach_rows([res.rows], [gsrc], res.global_idx, res.K, tail=tail_user)[0]
@@ -648,7 +672,8 @@ BATCH_LANES = 3          # compress_batch's default: clips in flight (16 cfg5 cl
 
 
 def compress_batch(clips, tpf: int, base_scale: float = 0.25, in_flight: int = BATCH_LANES, gather: bool = True,
-                   own_storage: bool = False, params: Optional[PassParams] = None):
+                   own_storage: bool = False, score_dtype: Optional[torch.dtype] = None,
+                   params: Optional[PassParams] = None):
     """Compress several clips (a list of [F_i * tpf, D] tensors) with up to `in_flight` of them running
     concurrently, one HIP stream each.  A single pass leaves the GPU idle during its single-workgroup selection
     replays; further clips in flight fill those gaps (DESIGN.md "clips in flight"; every lane keeps a plan = a workspace).
@@ -656,6 +681,7 @@ def compress_batch(clips, tpf: int, base_scale: float = 0.25, in_flight: int = B
     over clips (lmms-eval, batch size 1 per rank).
     `tpf` may also be a sequence of one tokens-per-frame value per clip (videos of different grids).
     params: one PassParams for every clip of the batch (None: the reference's hyper-parameters).
+    score_dtype: as in `compress`, for every clip of the batch.
     Storage: for clips of ONE shape every result is a VIEW into batch-wide buffers (one allocation per output kind), so
     keeping any clip's rows / indices alive keeps the whole batch's buffers alive (n * capacity * D elements);
     own_storage=True hands every clip its own tensors instead (one extra device copy of the kept rows).
@@ -664,8 +690,8 @@ def compress_batch(clips, tpf: int, base_scale: float = 0.25, in_flight: int = B
     params = _norm_params(params)
     if _ag.wants_grad(*clips):
         return [_attach_clip(r, c) for r, c in zip(_compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage,
-                                                                   params), clips)]
-    return _compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage, params)
+                                                                   params, score_dtype), clips)]
+    return _compress_batch(clips, tpf, base_scale, in_flight, gather, own_storage, params, score_dtype)
 
 
 def _attach_clip(res: CompressionResult, clip: torch.Tensor) -> CompressionResult:
@@ -675,7 +701,7 @@ def _attach_clip(res: CompressionResult, clip: torch.Tensor) -> CompressionResul
 
 
 def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool, own_storage: bool,
-                    params: Optional[PassParams] = None):
+                    params: Optional[PassParams] = None, score_dtype: Optional[torch.dtype] = None):
     clips = [_prep(c, "clip") for c in clips]
     if not clips:
         return []
@@ -690,6 +716,7 @@ def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool,
         if x.dim() != 2 or t <= 0 or x.shape[0] % t != 0:
             raise RuntimeError(f"clip {i}: shape {tuple(x.shape)} is not [frames * {t}, dim]")
         _c_params(params, x.shape[1])      # (the channel count's limits, before anything is enqueued for any clip)
+        _norm_score_dtype(score_dtype, x.dtype)
     cur = torch.cuda.current_stream(dev)
     lanes = [cur] + _lane_streams(dev, max(1, min(int(in_flight), len(clips))) - 1)
     plans = {}
@@ -699,7 +726,7 @@ def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool,
         if key not in plans:
             with torch.cuda.stream(lanes[j]):
                 plans[key] = _cached_plan(x.shape[0] // t, t, x.shape[1], x.dtype, dev, base_scale, "linear", 0, False,
-                                          gather, 0, params=params)
+                                          gather, 0, params=params, score_dtype=score_dtype)
         return plans[key]
 
     # Clips of one shape (the batched-eval case, BASELINE config 5): ONE allocation per output kind for the whole batch --
@@ -733,13 +760,13 @@ def _compress_batch(clips, tpf, base_scale: float, in_flight: int, gather: bool,
     words = (batch.kout if batch is not None else torch.stack([o.kout for o in outs])).tolist()   # the single host sync
     res = [o.result(K, status) for o, (K, status) in zip(outs, words)]
     if batch is not None:
-        _check_budgets(batch.ks, tpfs[0], clips[0].dtype)
+        _check_budgets(batch.ks, tpfs[0], plan_on(0, clips[0], tpfs[0]).arith_dtype)
         if own_storage:
             res = [CompressionResult(None if r.rows is None else r.rows.clone(), r.global_idx.clone(), r.ks.clone(), r.K)
                    for r in res]
     else:
         for r, t, x in zip(res, tpfs, clips):
-            _check_budgets(r.ks, t, x.dtype)
+            _check_budgets(r.ks, t, x.dtype if _norm_score_dtype(score_dtype, x.dtype) is None else torch.float32)
     return res
 
 
