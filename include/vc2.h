@@ -222,7 +222,7 @@ int64_t vc2_wait_host_count(const int64_t* K_host, double timeout_s);
  * channels < 1 or > D, a non-positive or non-finite temp or scale, n_alphas < 1: VC2_ERR_ARG; channels > 4096 or
  * n_alphas > 16: VC2_ERR_UNSUPPORTED; nothing is enqueued.  The workspace of vc2_workspace_bytes serves every set; every
  * numerics mode, VC2_FLAG_HAVE_STATS, tail_rows, the host mirror and both mappings work as without params.
- * The frame-sharded entry points below keep the reference's defaults: a parametrised sharded pass does not exist. */
+ * The frame-sharded pass takes the same set through the `_o` forms of its entry points (vc2_shard_opts, below). */
 typedef struct {
   int64_t channels;
   double temp;
@@ -252,7 +252,8 @@ int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
  * and channel limits are those of the storage dtype (D <= 8192, D % 8 == 0 for the vector path).  The workspace of
  * vc2_workspace_bytes(F, N, D, dtype) serves both passes: the fp32-scored one lays out the same arrays and needs none of
  * the replay engine's.
- * The stage entry points and the frame-sharded ones keep one dtype. */
+ * The stage entry points keep one dtype.  The frame-sharded `_o` forms take a score_dtype with these meanings and checks
+ * (vc2_shard_opts below): VC2_F32 over 16-bit rows is the fp32-scored pass across ranks. */
 int vc2_compress_ex4(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale,
                      int map_mode, int64_t grid_h, const void* gather_src, int64_t gather_rows,
                      void* ws, size_t ws_bytes, void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks,
@@ -475,12 +476,104 @@ int vc2_scores_phase2_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t
 /* Step 3 of the sharded path: s_all_f32[F_total] = the all-gathered per-frame uniqueness scores
  * (fp32-widened T values); budgets are computed over all F_total frames, selection + gather only for
  * this rank's frames [f0, f0+F_local).  idx_out holds LOCAL linear indices (f_local*N + n).  K_out is int64[3] here:
- * K_out[2] = the number of video-centre values within the replay margin of a T rounding boundary, which this path
- * leaves at the exactly rounded mean (mode 1; the unsharded pass replays torch's summation order for them). */
+ * K_out[2] = the number of video-centre values within the replay margin of a T rounding boundary that exchange 2b did
+ * not replay: they keep the exactly rounded mean (more flagged columns than `cap` in a mode without rounds; tail columns
+ * in the narrow record layout, see vc2_shard_opts). */
 int vc2_select_sharded(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t f0,
                        int64_t F_local, int64_t N, int64_t D, double base_scale, int dtype, void* ws,
                        size_t ws_bytes, int64_t* ks, int64_t* idx_out, int64_t cap, int64_t* K_out,
                        const void* gather_src, void* out_rows, void* stream);
+
+/* ---- the frame-sharded pass with options: the `_o` forms ---------------------------------------------------------
+ * Every sharded entry point that lays out the workspace or launches a parametrised kernel has a form with one trailing
+ * argument, `const vc2_shard_opts* opts`.  opts == NULL is the plain symbol (which forwards here with NULL): the same
+ * launches, arguments, record format and bits.  All `_o` calls of one pass, on every rank, must carry the same options.
+ *   params        the pass's hyper-parameters, as in vc2_compress_ex3: the same checks and error codes, before anything is
+ *                 enqueued (VC2_ERR_ARG / VC2_ERR_UNSUPPORTED; an entry point that takes C also refuses C !=
+ *                 params->channels).  channels is the k of vc2_chan_select and the C of phase 1 / phase 2 / the video-centre
+ *                 calls (C != D / 2: the row-interleaved sweep 2; C == D works; C > 4096 is refused); alphas go by value
+ *                 into sweep 3's epilogue from the phase-2 forms (a set equal to the reference's five: the compile-time
+ *                 path); temp is vc2_select_sharded_o's softmax temperature.  NULL or a set equal to the defaults: the
+ *                 default pass.
+ *   score_dtype   a public dtype code (0..2), checked as in vc2_compress_ex4 (anything but dtype itself, or VC2_F32 over
+ *                 VC2_BF16 / VC2_F16 rows: VC2_ERR_ARG).  VC2_F32 over 16-bit rows: x, gather_src and out_rows stay 16-bit,
+ *                 every kernel that reads rows loads them as stored and computes in fp32; total_f32 / s_f32 and the
+ *                 selection are the fp32-input pass's.  The caller reduces the exchanged block statistics with
+ *                 vc2_chan_var_from_stats(..., VC2_F32, ...): fp32 variances, which vc2_chan_select ranks through its 64-bit
+ *                 selection words.  There is no "torch order" replay in fp32 arithmetic: the vc2_video_centre_* forms
+ *                 enqueue nothing and K_out[2] is 0; exchanges 1-3 keep their fp64 / fp32 formats.  The workspace of
+ *                 vc2_workspace_bytes(F, N, D, dtype) serves this pass too.
+ *   tail_records  0: exchange 2b in the narrow record layout of vc2_video_centre_blocks (edge 64); video-centre columns in
+ *                 the C % 32 tail keep their exactly rounded mean and stay counted in K_out[2].
+ *                 1: the WIDE layout, which also replays the tail columns.  A tail column is one whose position in
+ *                 torch.topk's order (spos) is at or above (C / 32) * 32 -- (C / 4) * 4 when C < 8.  torch sums it with
+ *                 row_sum's four interleaved chains: chain k (0..3) is the cascade over the R_total / 4 values at video rows
+ *                 k + 4e with level power lp4 = level_power(R_total / 4), B4 = 2^lp4; the sum is chain0, + the R_total % 4
+ *                 leftover rows one by one, + chain1 + chain2 + chain3.  A level-0 block of a chain is the rows k + 4u of one
+ *                 aligned RUN of 4 * B4 video rows.  Record of one flagged column, 2 * 256 + R / 16 + 1 floats (R = F * N;
+ *                 ragged forms: the largest rank's rows), for plain and tail columns alike:
+ *                   [0, 256)    the x^ values of this rank's first h rows: the end of a block (plain column, h < B) or of a
+ *                               run (tail column, h < 4 * B4 <= 256) that began before this rank; row order
+ *                   [256, 512)  the x^ values of its last t rows: the beginning of a block / run that ends after it
+ *                   [512, ..)   plain column: the sums of its complete blocks.  Tail column: for every run it holds
+ *                               completely four sums, one per chain, rows added in row order (stride 4): [4 * run + k]
+ *                 The video's last R_total mod (4 * B4) rows (the chains' leftover elements, the R_total % 4 leftover rows)
+ *                 lie in no complete run and arrive raw.  The finish kernels run the four cascades over the gathered
+ *                 records, a straddling run's rows one by one from however many ranks it meets, combine them in the order
+ *                 above, write the mean and take the column off the count.  Equal and ragged layouts, rounds included.
+ * One vc2_workspace_bytes(F, N, D, dtype) workspace serves every combination.  vc2_chan_var_from_stats, vc2_chan_select
+ * and vc2_video_centre_flagged need no `_o` form. */
+typedef struct {
+  const vc2_pass_params* params;
+  int32_t score_dtype;
+  int32_t tail_records;
+} vc2_shard_opts;
+int vc2_chan_stats_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, int64_t F_total, int block_frames,
+                     void* ws, size_t ws_bytes, double* bstats, void* stream, const vc2_shard_opts* opts);
+int vc2_scores_phase1_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                        int64_t C, int32_t* spos, const int32_t* perm, const float* var_f32, int64_t F_total,
+                        void* ws, size_t ws_bytes, double* csum_parts, void* stream, const vc2_shard_opts* opts);
+int vc2_video_centre_blocks_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                              int64_t C, const int32_t* spos, const double* csum_all, int64_t P,
+                              int64_t csum_stride, int64_t rows_per_rank, int64_t R_total, int64_t row0, void* ws,
+                              size_t ws_bytes, float* blocks_out, int cap, void* stream, const vc2_shard_opts* opts);
+int vc2_scores_phase2_blocks_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                               int64_t C, const int32_t* spos, const double* csum_all, int64_t P,
+                               int64_t csum_stride, int64_t rows_per_rank, int64_t R_total, void* ws, size_t ws_bytes,
+                               void* v_T, void* f_T, float* total_f32, float* s_f32, const float* blocks_all, int world,
+                               int cap, void* stream, const vc2_shard_opts* opts);
+int vc2_video_centre_blocks_round_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                    int64_t C, const int32_t* spos, int64_t R_total, int64_t row0, void* ws,
+                                    size_t ws_bytes, float* blocks_out, int cap, int col_offset, void* stream,
+                                    const vc2_shard_opts* opts);
+int vc2_video_centre_finish_round_o(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
+                                    int64_t R_total, void* ws, size_t ws_bytes, const float* blocks_all, int world,
+                                    int cap, int col_offset, void* stream, const vc2_shard_opts* opts);
+int vc2_video_centre_blocks_ragged_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                     int64_t C, const int32_t* spos, const double* csum_all, int64_t P,
+                                     int64_t csum_stride, int64_t rows_per_rank, int64_t R_total,
+                                     const int64_t* rank_rows /* host [world] */, int world, int rank, void* ws,
+                                     size_t ws_bytes, float* blocks_out, int cap, void* stream,
+                                     const vc2_shard_opts* opts);
+int vc2_video_centre_blocks_round_ragged_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype,
+                                           const int32_t* cols, int64_t C, const int32_t* spos, int64_t R_total,
+                                           const int64_t* rank_rows /* host [world] */, int world, int rank, void* ws,
+                                           size_t ws_bytes, float* blocks_out, int cap, int col_offset, void* stream,
+                                           const vc2_shard_opts* opts);
+int vc2_video_centre_finish_round_ragged_o(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
+                                           int64_t R_total, const int64_t* rank_rows /* host [world] */, int world,
+                                           int rank, void* ws, size_t ws_bytes, const float* blocks_all, int cap,
+                                           int col_offset, void* stream, const vc2_shard_opts* opts);
+int vc2_scores_phase2_blocks_ragged_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                      int64_t C, const int32_t* spos, const double* csum_all, int64_t P,
+                                      int64_t csum_stride, int64_t rows_per_rank, int64_t R_total,
+                                      const int64_t* rank_rows /* host [world] */, int world, int rank, void* ws,
+                                      size_t ws_bytes, void* v_T, void* f_T, float* total_f32, float* s_f32,
+                                      const float* blocks_all, int cap, void* stream, const vc2_shard_opts* opts);
+int vc2_select_sharded_o(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t f0,
+                         int64_t F_local, int64_t N, int64_t D, double base_scale, int dtype, void* ws,
+                         size_t ws_bytes, int64_t* ks, int64_t* idx_out, int64_t cap, int64_t* K_out,
+                         const void* gather_src, void* out_rows, void* stream, const vc2_shard_opts* opts);
 
 /* _multi_scale_gaussian(x, center, alphas) as a standalone call -- vidcom2.py:59-62 (the fused pass
  * never materialises x; this entry serves callers of the helper itself).  x: T[F*N, C] as given,

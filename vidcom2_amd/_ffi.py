@@ -96,6 +96,13 @@ _SIGNATURES = {
 }
 _RESTYPES = {"vc2_kept_capacity": _i64, "vc2_wait_host_count": _i64,  "vc2_last_error": ctypes.c_char_p, "vc2_version": ctypes.c_char_p}
 
+# the frame-sharded entry points' `_o` forms: the plain signature and a trailing `const vc2_shard_opts*` (include/vc2.h)
+for _name in ("vc2_chan_stats", "vc2_scores_phase1", "vc2_video_centre_blocks", "vc2_scores_phase2_blocks",
+              "vc2_video_centre_blocks_round", "vc2_video_centre_finish_round", "vc2_video_centre_blocks_ragged",
+              "vc2_video_centre_blocks_round_ragged", "vc2_video_centre_finish_round_ragged",
+              "vc2_scores_phase2_blocks_ragged", "vc2_select_sharded"):
+    _SIGNATURES[_name + "_o"] = _SIGNATURES[_name] + [_vp]
+
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 

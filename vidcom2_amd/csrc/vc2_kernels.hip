@@ -2816,12 +2816,30 @@ __global__ __launch_bounds__(64) void k_video_centre(const double* __restrict__ 
 // The records are all-gathered (rank order = row order) and k_vc_finish runs the rest of torch's cascade over the
 // whole video: a straddling block is its rows' raw values added one by one in row order -- from as many ranks as it
 // meets (a rank with fewer rows than a block is all head); the video's last R_total % B rows (the cascade's tail) come
-// the same way.  Needs the cascade's plain form (column in a full group of 32).  Ranks with equal row counts are located by
+// the same way.  (The cascade's plain form: a column in a full group of 32; the others below.)  Ranks with equal row counts are located by
 // division (k_vc_blocks / k_vc_finish); unequal ones through a prefix table (the _ragged kernels, same body).  More
 // flagged columns than a record buffer holds go in further rounds (slot offset j0).
 constexpr int kVcEdge = 64;
-__host__ __device__ inline int64_t vc_rec_floats(int64_t R_local) { return 2 * kVcEdge + R_local / 16 + 1; }
+// TAIL COLUMNS (position in torch.topk's order at or above (C / 32) * 32; C / 4 * 4 when C < 8): torch sums them with
+// row_sum's four interleaved chains (wave_column_solo(simple = false)): chain k is the cascade over the R_total / 4 values
+// at video rows k + 4e, with its own level power lp4 = cascade_lp(R_total / 4) and B4 = 2^lp4.  A level-0 block of chain k
+// is the rows k + 4u of one aligned RUN of 4 * B4 video rows, so the record of a tail column goes by runs:
+//     [0, E)     the x^ values of my first h rows (the end of a run begun before me), in row order;  E = kVcEdgeTail
+//     [E, 2E)    the x^ values of my last t rows (the beginning of a run that ends after me)
+//     [2E, ..)   for every run I hold completely four sums, one per chain (rows added in row order, stride 4)
+// The video's last R_total mod (4 * B4) rows -- the chains' leftover elements and the R_total % 4 leftover rows -- are in
+// no complete run, so they arrive raw the same way.  Records of tail columns exist only in the WIDE layout (edge E = 256
+// for plain and tail columns alike, one stride 2 * 256 + R_local / 16 + 1: a rank holds at most R_local / 64 runs); the
+// narrow layout (edge 64) carries plain columns only and leaves tail columns at their exactly rounded mean, counted.
+constexpr int kVcEdgeTail = 256;
+__host__ __device__ inline int64_t vc_rec_floats(int64_t R_local, int edge = kVcEdge) { return 2 * edge + R_local / 16 + 1; }
 __host__ __device__ inline int vc_head_rows(int64_t row0, int B) { return int((B - row0 % B) % B); }
+// the layout of one exchange-2b round: edge = kVcEdge, lp4 = -1 (narrow: no tail columns) or kVcEdgeTail, cascade_lp(R_total / 4)
+struct VcLayout { int edge; int lp4; };
+__host__ __device__ inline bool vc_tail_column(int C, int sp) {
+  const int group = C >= 8 ? 32 : 4;
+  return sp >= (C / group) * group;
+}
 __device__ __forceinline__ int nth_flagged_column(const uint8_t* __restrict__ vflag, int C, int j, int lane) {
   // lane-contiguous chunks, wave scan; returns the column of the j-th set flag or -1 (same value in every lane)
   const int E = (C + 63) / 64;
@@ -2841,43 +2859,61 @@ __device__ __forceinline__ int nth_flagged_column(const uint8_t* __restrict__ vf
 
 template <int DT>
 __device__ __forceinline__ void vc_blocks_body(const uint8_t* __restrict__ vflag, int C, const void* __restrict__ x,
-                                               int D, const int* __restrict__ cols, const float* __restrict__ den,
-                                               int64_t R_local, int64_t row0, int lp, float* __restrict__ blocks_out,
-                                               int j0, int64_t rec_floats) {
+                                               int D, const int* __restrict__ cols, const int* __restrict__ spos,
+                                               const float* __restrict__ den, int64_t R_local, int64_t row0, int lp,
+                                               float* __restrict__ blocks_out, int j0, int64_t rec_floats,
+                                               const VcLayout lay) {
   const int lane = threadIdx.x, j = blockIdx.y;                  // record j of this round = flagged column number j0 + j
   const int cc = nth_flagged_column(vflag, C, j0 + j, lane);
   if (cc < 0) return;
   const int col = cols ? cols[cc] : cc;
+  float* rec = blocks_out + int64_t(j) * rec_floats;
+  const int E = lay.edge;
+  if (vc_tail_column(C, spos ? spos[cc] : cc)) {                 // four interleaved chains: the record goes by runs
+    if (lay.lp4 < 0) return;                                     // (narrow layout: not replayed)
+    const int run = 4 << lay.lp4;
+    const int h = int(min<int64_t>(R_local, vc_head_rows(row0, run)));
+    const int64_t nr = (R_local - h) / run;
+    const int t = int(R_local - h - nr * run);
+    if (blockIdx.x == gridDim.x - 1) {                           // the raw edges (h, t < run <= 256)
+      for (int i = lane; i < h; i += 64) rec[i] = xhat_at<DT>(x, i, D, col, den);
+      for (int i = lane; i < t; i += 64) rec[E + i] = xhat_at<DT>(x, h + nr * run + i, D, col, den);
+      return;
+    }
+    const int64_t b = int64_t(blockIdx.x) * 64 + lane;           // run b / 4, chain b % 4
+    if (b >= 4 * nr) return;
+    rec[2 * E + b] = block_sum_rows<DT>(x, D, col, den, h + (b >> 2) * run + (b & 3), 4, 0, lay.lp4);
+    return;
+  }
   const int B = 1 << lp;
   const int h = int(min<int64_t>(R_local, vc_head_rows(row0, B)));
   const int64_t nb = (R_local - h) >> lp;
   const int t = int(R_local - h - (nb << lp));
-  float* rec = blocks_out + int64_t(j) * rec_floats;
   if (blockIdx.x == gridDim.x - 1) {                            // the raw edges
     if (lane < h) rec[lane] = xhat_at<DT>(x, lane, D, col, den);
-    if (lane < t) rec[kVcEdge + lane] = xhat_at<DT>(x, h + (nb << lp) + lane, D, col, den);
+    if (lane < t) rec[E + lane] = xhat_at<DT>(x, h + (nb << lp) + lane, D, col, den);
     return;
   }
   const int64_t b = int64_t(blockIdx.x) * 64 + lane;
   if (b >= nb) return;
-  rec[2 * kVcEdge + b] = block_sum_rows<DT>(x, D, col, den, h, 1, b << lp, lp);
+  rec[2 * E + b] = block_sum_rows<DT>(x, D, col, den, h, 1, b << lp, lp);
 }
 template <int DT>
 __global__ __launch_bounds__(64) void k_vc_blocks(const uint8_t* __restrict__ vflag, int C, const void* __restrict__ x,
                                                   int D, const int* __restrict__ cols, const int* __restrict__ spos,
                                                   const float* __restrict__ den, int64_t R_local, int64_t row0, int lp,
-                                                  float* __restrict__ blocks_out, int j0) {
-  (void)spos;
-  vc_blocks_body<DT>(vflag, C, x, D, cols, den, R_local, row0, lp, blocks_out, j0, vc_rec_floats(R_local));
+                                                  float* __restrict__ blocks_out, int j0, const VcLayout lay) {
+  vc_blocks_body<DT>(vflag, C, x, D, cols, spos, den, R_local, row0, lp, blocks_out, j0, vc_rec_floats(R_local, lay.edge), lay);
 }
 // unequal ranks: the records of all ranks share the stride of the rank with the most rows (one rectangular all-gather)
 template <int DT>
 __global__ __launch_bounds__(64) void k_vc_blocks_ragged(const uint8_t* __restrict__ vflag, int C,
                                                          const void* __restrict__ x, int D, const int* __restrict__ cols,
+                                                         const int* __restrict__ spos,
                                                          const float* __restrict__ den, int64_t R_local, int64_t row0,
                                                          int lp, float* __restrict__ blocks_out, int j0,
-                                                         int64_t rec_floats) {
-  vc_blocks_body<DT>(vflag, C, x, D, cols, den, R_local, row0, lp, blocks_out, j0, rec_floats);
+                                                         int64_t rec_floats, const VcLayout lay) {
+  vc_blocks_body<DT>(vflag, C, x, D, cols, spos, den, R_local, row0, lp, blocks_out, j0, rec_floats, lay);
 }
 
 // Which rank holds video row r, and what that rank holds.  Equal ranks: a division.  Unequal ranks (the ragged entry
@@ -2885,10 +2921,11 @@ __global__ __launch_bounds__(64) void k_vc_blocks_ragged(const uint8_t* __restri
 // searched from LDS.  No rank is empty, so a row has one owner.
 struct VcEqualRanks {
   int64_t R_local;
+  int edge;
   __device__ __forceinline__ int64_t owner(int64_t r) const { return r / R_local; }
   __device__ __forceinline__ int64_t row0(int64_t w) const { return w * R_local; }
   __device__ __forceinline__ int64_t rows(int64_t) const { return R_local; }
-  __device__ __forceinline__ int64_t rec_floats() const { return vc_rec_floats(R_local); }
+  __device__ __forceinline__ int64_t rec_floats() const { return vc_rec_floats(R_local, edge); }
 };
 constexpr int kVcMaxWorld = VC2_RAGGED_MAX_WORLD;
 struct VcRankTable { int64_t pre[kVcMaxWorld + 1]; int64_t rec; int world; };   // pre[w] = video row of rank w's first row
@@ -2909,19 +2946,78 @@ struct VcRaggedRanks {
   __device__ __forceinline__ int64_t rec_floats() const { return rec; }
 };
 
+// a tail column from the all-gathered records: the four chains' cascades one after the other (each like a plain column's,
+// over runs instead of blocks), then row_sum's order -- chain 0, the R_total % 4 leftover rows one by one, chains 1, 2, 3
+template <int DT, class Ranks>
+__device__ __forceinline__ float vc_finish_tail(const float* __restrict__ blocks_all, int cap, int j, const Ranks& rk,
+                                                int64_t R_total, const VcLayout lay, float* l1, float* tailv) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int E = lay.edge, lp4 = lay.lp4, B4 = 1 << lp4, run = 4 << lp4;
+  const int64_t rec = rk.rec_floats();
+  auto record = [&](int64_t w) { return blocks_all + (w * cap + j) * rec; };
+  auto head_of = [&](int64_t w) { return int(min<int64_t>(rk.rows(w), vc_head_rows(rk.row0(w), run))); };
+  auto row_value = [&](int64_t r) -> float {                     // raw: a row of a run no rank holds completely
+    const int64_t w = rk.owner(r), off = r - rk.row0(w);
+    const int h = head_of(w);
+    if (off < h) return record(w)[off];
+    const int64_t nr = (rk.rows(w) - h) / run;
+    return record(w)[E + (off - h - nr * run)];
+  };
+  auto block_value = [&](int64_t b, int k) -> float {            // level-0 block b of chain k = rows k + 4u of run b
+    const int64_t g0 = b * run, w = rk.owner(g0), off = g0 - rk.row0(w);
+    const int h = head_of(w);
+    const int64_t nr = (rk.rows(w) - h) / run;
+    if (off >= h && (off - h) % run == 0 && (off - h) / run < nr) return record(w)[2 * E + 4 * ((off - h) / run) + k];
+    float a = row_value(g0 + k);
+    for (int u = 1; u < B4; ++u) a += row_value(g0 + k + 4 * u);
+    return a;
+  };
+  const int64_t q4 = R_total >> 2, nb4 = q4 >> lp4;
+  const int G1 = int((nb4 + B4 - 1) >> lp4);
+  const int ntail = int(q4 - (nb4 << lp4));                      // a chain's leftover elements (< B4 <= 64)
+  float part[4];
+  for (int k = 0; k < 4; ++k) {
+    __syncthreads();                                             // (the previous chain's cascade has read l1 / tailv)
+    for (int g = tid; g < G1; g += 256) {
+      const int64_t b0 = int64_t(g) << lp4;
+      const int nbl = int(min<int64_t>(B4, nb4 - b0));
+      float a = 0.f;
+      for (int u = 0; u < nbl; ++u) {
+        const float t = block_value(b0 + u, k);
+        a = u == 0 ? t : a + t;
+      }
+      l1[g] = a;
+    }
+    if (tid < ntail) tailv[tid] = row_value(nb4 * run + k + 4 * int64_t(tid));
+    __syncthreads();
+    part[k] = wave_cascade_final<DT>(l1, nb4, nullptr, 0, 0, nullptr, 0, 1, q4, lane, lp4, tailv);   // (every wave: same value)
+  }
+  float s = part[0];
+  for (int64_t i = q4 << 2; i < R_total; ++i) s += row_value(i);
+  s += part[1]; s += part[2]; s += part[3];
+  return s;
+}
+
 template <int DT, class Ranks>
 __device__ __forceinline__ void vc_finish_body(const uint8_t* __restrict__ vflag, int C, const int* __restrict__ spos,
                                                const float* __restrict__ blocks_all, int cap, const Ranks rk,
                                                int64_t R_total, float* __restrict__ vc, int* __restrict__ fragile_count,
-                                               int j0) {
+                                               int j0, const VcLayout lay) {
   __shared__ float l1[kL1Cap + 4];
   __shared__ float tailv[kVcEdge];
   const int tid = threadIdx.x, lane = tid & 63, j = blockIdx.x;  // record j of this round = flagged column number j0 + j
   const int cc = nth_flagged_column(vflag, C, j0 + j, lane);
   if (cc < 0) return;
-  const int group = C >= 8 ? 32 : 4;
-  const int sp = spos ? spos[cc] : cc;
-  if (sp >= (C / group) * group) return;                        // row_sum's interleaved chains: not replayed here
+  const int E = lay.edge;
+  if (vc_tail_column(C, spos ? spos[cc] : cc)) {                // row_sum's interleaved chains
+    if (lay.lp4 < 0) return;                                    // (narrow layout: not replayed, stays counted)
+    const float s = vc_finish_tail<DT>(blocks_all, cap, j, rk, R_total, lay, l1, tailv);
+    if (tid == 0) {
+      vc[cc] = rnT<DT>(s / float(R_total));
+      if (fragile_count) atomicSub(fragile_count, 1);
+    }
+    return;
+  }
   const int lp = cascade_lp(R_total), B = 1 << lp;
   const int64_t rec = rk.rec_floats();
   auto record = [&](int64_t w) { return blocks_all + (w * cap + j) * rec; };
@@ -2933,7 +3029,7 @@ __device__ __forceinline__ void vc_finish_body(const uint8_t* __restrict__ vflag
     const int h = head_of(w);
     if (off < h) return record(w)[off];
     const int64_t nb = (rk.rows(w) - h) >> lp;
-    return record(w)[kVcEdge + (off - h - (nb << lp))];
+    return record(w)[E + (off - h - (nb << lp))];
   };
   // the level-0 sum of the video's block b: a rank's own complete block, or -- a block that meets two OR MORE ranks
   // (ranks with fewer rows than a block included) -- its rows one by one in row order
@@ -2941,7 +3037,7 @@ __device__ __forceinline__ void vc_finish_body(const uint8_t* __restrict__ vflag
     const int64_t g0 = b << lp, w = rk.owner(g0), off = g0 - rk.row0(w);
     const int h = head_of(w);
     const int64_t nb = (rk.rows(w) - h) >> lp;
-    if (off >= h && ((off - h) & (B - 1)) == 0 && ((off - h) >> lp) < nb) return record(w)[2 * kVcEdge + ((off - h) >> lp)];
+    if (off >= h && ((off - h) & (B - 1)) == 0 && ((off - h) >> lp) < nb) return record(w)[2 * E + ((off - h) >> lp)];
     float a = row_value(g0);
     for (int u = 1; u < B; ++u) a += row_value(g0 + u);
     return a;
@@ -2973,20 +3069,21 @@ template <int DT>
 __global__ __launch_bounds__(256) void k_vc_finish(const uint8_t* __restrict__ vflag, int C,
                                                    const int* __restrict__ spos, const float* __restrict__ blocks_all,
                                                    int world, int cap, int64_t R_local, int64_t R_total,
-                                                   float* __restrict__ vc, int* __restrict__ fragile_count, int j0) {
+                                                   float* __restrict__ vc, int* __restrict__ fragile_count, int j0,
+                                                   const VcLayout lay) {
   (void)world;
-  vc_finish_body<DT>(vflag, C, spos, blocks_all, cap, VcEqualRanks{R_local}, R_total, vc, fragile_count, j0);
+  vc_finish_body<DT>(vflag, C, spos, blocks_all, cap, VcEqualRanks{R_local, lay.edge}, R_total, vc, fragile_count, j0, lay);
 }
 template <int DT>
 __global__ __launch_bounds__(256) void k_vc_finish_ragged(const uint8_t* __restrict__ vflag, int C,
                                                           const int* __restrict__ spos,
                                                           const float* __restrict__ blocks_all, int cap,
                                                           const VcRankTable tab, int64_t R_total, float* __restrict__ vc,
-                                                          int* __restrict__ fragile_count, int j0) {
+                                                          int* __restrict__ fragile_count, int j0, const VcLayout lay) {
   __shared__ int64_t pre[kVcMaxWorld + 1];
   if (int(threadIdx.x) <= tab.world) pre[threadIdx.x] = tab.pre[threadIdx.x];
   __syncthreads();
-  vc_finish_body<DT>(vflag, C, spos, blocks_all, cap, VcRaggedRanks{pre, tab.rec, tab.world}, R_total, vc, fragile_count, j0);
+  vc_finish_body<DT>(vflag, C, spos, blocks_all, cap, VcRaggedRanks{pre, tab.rec, tab.world}, R_total, vc, fragile_count, j0, lay);
 }
 
 // a caller's Gaussian scales, passed BY VALUE to the kernels that take them (k_multi_scale_gaussian, and k_dist's
@@ -4759,11 +4856,11 @@ int check_launch(const char* what) {
 // ---- optional per-kernel timing (bench.py's roofline leg): hipEvents around every launch --------
 enum KernelId { KID_STATS = 0, KID_STATS_REDUCE, KID_CHAN_SELECT, KID_NORM_COLSUM, KID_CENTRES, KID_DIST,
                 KID_EPILOGUE, KID_SCALES, KID_KS, KID_SELECT, KID_GATHER_ROWS, KID_OTHER, KID_CHAN_ORDER, KID_DIST_FIX,
-                KID_CENTRE_FIX, KID_COUNT };
+                KID_CENTRE_FIX, KID_VC_RECORDS, KID_COUNT };
 const char* const kKernelNames[KID_COUNT] = {"k_chan_stats", "k_stats_reduce", "k_chan_select", "k_norm_colsum",
                                              "k_centres", "k_dist", "k_token_epilogue", "k_scales", "k_ks(unused)",
                                              "k_select", "k_gather_rows", "k_norm_fix", "k_chan_order",
-                                             "k_dist_fix", "k_centre_fix"};
+                                             "k_dist_fix", "k_centre_fix", "k_vc_records"};
 struct ProfRec { int id; hipEvent_t a, b; };
 bool g_prof = false;                // (bench-only; the record list is mutex-protected)
 std::mutex g_prof_mu;
@@ -4842,8 +4939,8 @@ int launch_chan_stats(const Plan& p, const void* x, void* ws, double* bstats, vo
   if (!have_partials) { int rcs = launch_stats_sweep(p, x, ws, PoolSrc{}, st); if (rcs) return rcs; }
   { ProfScope ps_(KID_STATS_REDUCE, st);
   const PartSrc src{part, x, p.R, p.BF * p.stat_splits, p.G, int(p.N), p.BF};
-  if (bstats)         // the frame-sharded pass needs the block statistics themselves (exchange 1)
-    VC2_DISPATCH_DT(p.dt, hipLaunchKernelGGL((k_block_stats<DT>), dim3(unsigned(cdiv(p.D, 64)), unsigned(p.NB)), dim3(64),
+  if (bstats)         // the frame-sharded pass needs the block statistics themselves (exchange 1; fp64 of raw values: the storage dtype's kernel)
+    VC2_DISPATCH_DT(st_of(p.dt),hipLaunchKernelGGL((k_block_stats<DT>), dim3(unsigned(cdiv(p.D, 64)), unsigned(p.NB)), dim3(64),
                                              0, st, src, int(p.D), bstats));
   if (var_f32 || var_T) {
     const int64_t n_each = int64_t(p.BF) * p.N, n_last = p.R - int64_t(p.NB - 1) * n_each;
@@ -5299,17 +5396,84 @@ int64_t vc2_kept_capacity(int64_t F, int64_t N, double base_scale) {
   return int64_t(cap < full ? cap : full);
 }
 
+// the reference's hyper-parameters: int(D * 0.5) channels (vidcom2.py:41), temp 0.01 (:66), alphas 2^-3 .. 2^1 (:54)
+constexpr double kRefTemp = 0.01;
+constexpr double kRefAlphas[5] = {0.125, 0.25, 0.5, 1.0, 2.0};
+
+// a pass's hyper-parameters, checked (vc2.h, vc2_compress_ex3): nothing may be enqueued on a bad set.  A set equal to the
+// reference's is the default pass (al == nullptr: the compile-time scales)
+struct PassSet {
+  int64_t kc; double temp; MsgAlphas alphas; bool own_scales;
+  const MsgAlphas* al() const { return own_scales ? &alphas : nullptr; }
+};
+static int check_pass_params(const vc2_pass_params* params, int64_t D, PassSet* ps) {
+  ps->kc = int64_t(double(D) * 0.5);                      // int(x.shape[-1] * ratio), vidcom2.py:41
+  ps->temp = kRefTemp;
+  ps->own_scales = false;
+  if (!params) return VC2_OK;
+  if (params->channels < 1 || params->channels > D)
+    return fail(VC2_ERR_ARG, "params: %lld channels of %lld", (long long)params->channels, (long long)D);
+  if (!(params->temp > 0.0) || !std::isfinite(params->temp)) return fail(VC2_ERR_ARG, "params: temp must be finite and > 0");
+  if (params->n_alphas < 1) return fail(VC2_ERR_ARG, "params: no Gaussian scales");
+  if (params->n_alphas > kMaxAlphas) return fail(VC2_ERR_UNSUPPORTED, "params: more than %d Gaussian scales", kMaxAlphas);
+  for (int i = 0; i < params->n_alphas; ++i)
+    if (!(params->alphas[i] > 0.0) || !std::isfinite(params->alphas[i]))
+      return fail(VC2_ERR_ARG, "params: Gaussian scale %d must be finite and > 0", i);
+  if (params->channels > 4096) return fail(VC2_ERR_UNSUPPORTED, "params: more than 4096 scored channels");
+  ps->kc = params->channels;
+  ps->temp = params->temp;
+  bool ref_scales = params->n_alphas == 5;
+  for (int i = 0; ref_scales && i < 5; ++i) ref_scales = params->alphas[i] == kRefAlphas[i];
+  if (!ref_scales) {
+    ps->alphas.n = params->n_alphas;
+    for (int i = 0; i < kMaxAlphas; ++i)                 // python: -d / (2 * a), scalar -> fp32
+      ps->alphas.two_a[i] = i < params->n_alphas ? float(2.0 * params->alphas[i]) : 1.0f;
+    ps->own_scales = true;
+  }
+  return VC2_OK;
+}
+
+// the options of the frame-sharded `_o` entry points (vc2.h, vc2_shard_opts), checked.  opts == NULL -- what the plain
+// symbols forward -- is the plain pass: the reference's defaults, one dtype, narrow exchange-2b records.
+struct ShardOpts { int pdt; PassSet ps; bool have_params; bool tail; };
+static int shard_opts(const vc2_shard_opts* o, int dtype, int64_t D, int64_t C, ShardOpts* so) {
+  so->pdt = dtype; so->have_params = false; so->tail = false;
+  if (!o) return check_pass_params(nullptr, D, &so->ps);
+  if (dtype < VC2_F32 || dtype > VC2_F16) return fail(VC2_ERR_ARG, "unknown dtype code %d", dtype);
+  if (o->score_dtype != dtype && !(o->score_dtype == VC2_F32 && (dtype == VC2_BF16 || dtype == VC2_F16)))
+    return fail(VC2_ERR_ARG, "score_dtype %d with dtype %d: it must equal dtype, or be VC2_F32 over 16-bit rows", o->score_dtype, dtype);
+  int rc = check_pass_params(o->params, D, &so->ps);
+  if (rc) return rc;
+  if (o->params && C > 0 && C != o->params->channels)
+    return fail(VC2_ERR_ARG, "C=%lld, but the options' params name %lld channels", (long long)C, (long long)o->params->channels);
+  // VC2_F32 over 16-bit rows: the library's storage / arithmetic pair, as in vc2_compress_ex4 -- 16-bit loads, fp32
+  // arithmetic, hence no "torch order" replay (vc_blocks_ok is false) and no exchange-2b records of either layout
+  if (o->score_dtype != dtype) so->pdt = dtype == VC2_BF16 ? VC2_BF16_A32 : VC2_F16_A32;
+  so->have_params = o->params != nullptr;
+  so->tail = o->tail_records != 0 && so->pdt == dtype;
+  return VC2_OK;
+}
+static VcLayout vc_layout(const ShardOpts& so, int64_t R_total) {
+  return so.tail ? VcLayout{kVcEdgeTail, cascade_lp(R_total >> 2)} : VcLayout{kVcEdge, -1};
+}
+
 int vc2_stat_block_frames(void) { return kStatBlockFrames; }
 
-int vc2_chan_stats(const void* x, int64_t F, int64_t N, int64_t D, int dtype, int64_t F_total, int block_frames,
-                   void* ws, size_t ws_bytes, double* bstats, void* stream) {
+int vc2_chan_stats_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, int64_t F_total, int block_frames,
+                   void* ws, size_t ws_bytes, double* bstats, void* stream, const vc2_shard_opts* opts) {
   if (!x || !bstats) return fail(VC2_ERR_ARG, "null pointer");
   if (block_frames < 1 || block_frames > kStatBlockFrames) return fail(VC2_ERR_ARG, "block_frames must be 1..%d", kStatBlockFrames);
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, 0, &so); if (rco) return rco; }
   Plan p;
-  int rc = make_plan(F, N, D, dtype, &p, F_total, block_frames);
+  int rc = make_plan(F, N, D, so.pdt, &p, F_total, block_frames, opts != nullptr);
   if (rc) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
   return launch_chan_stats(p, x, ws, bstats, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+int vc2_chan_stats(const void* x, int64_t F, int64_t N, int64_t D, int dtype, int64_t F_total, int block_frames,
+                   void* ws, size_t ws_bytes, double* bstats, void* stream) {
+  return vc2_chan_stats_o(x, F, N, D, dtype, F_total, block_frames, ws, ws_bytes, bstats, stream, nullptr);
 }
 
 int vc2_chan_var_from_stats(const double* bstats, int64_t NB, int64_t rows_per_block, int64_t R_total, int64_t D,
@@ -5372,14 +5536,16 @@ static int check_cols(const int32_t* cols, int64_t C, int64_t D) {
   return VC2_OK;
 }
 
-int vc2_scores_phase1(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
+int vc2_scores_phase1_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
                       int32_t* spos, const int32_t* perm, const float* var_f32, int64_t F_total, void* ws,
-                      size_t ws_bytes, double* csum_parts, void* stream) {
+                      size_t ws_bytes, double* csum_parts, void* stream, const vc2_shard_opts* opts) {
   if (!x) return fail(VC2_ERR_ARG, "x is null");
   if (perm && !(var_f32 && cols && spos)) return fail(VC2_ERR_ARG, "the ORDER rider needs perm, var_f32, cols and spos");
   { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
   Plan p;
-  int rc = make_plan(F, N, D, dtype, &p, F_total);
+  int rc = make_plan(F, N, D, so.pdt, &p, F_total, 0, opts != nullptr);
   if (rc) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -5399,6 +5565,11 @@ int vc2_scores_phase1(const void* x, int64_t F, int64_t N, int64_t D, int dtype,
   }
   return VC2_OK;
 }
+int vc2_scores_phase1(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
+                      int32_t* spos, const int32_t* perm, const float* var_f32, int64_t F_total, void* ws,
+                      size_t ws_bytes, double* csum_parts, void* stream) {
+  return vc2_scores_phase1_o(x, F, N, D, dtype, cols, C, spos, perm, var_f32, F_total, ws, ws_bytes, csum_parts, stream, nullptr);
+}
 
 // can the frame-sharded pass replay its video-centre means (see k_vc_blocks)?
 static bool vc_blocks_ok(const Plan& p, int64_t R_total, int strict) {
@@ -5407,19 +5578,22 @@ static bool vc_blocks_ok(const Plan& p, int64_t R_total, int strict) {
   return strict != 0 && at_of(p.dt) != VC2_F32 && R_total % p.R == 0 && cascade_modelled(R_total);
 }
 
-int vc2_video_centre_blocks(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
+int vc2_video_centre_blocks_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
                             const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
                             int64_t rows_per_rank, int64_t R_total, int64_t row0, void* ws, size_t ws_bytes,
-                            float* blocks_out, int cap, void* stream) {
+                            float* blocks_out, int cap, void* stream, const vc2_shard_opts* opts) {
   if (!x || !csum_all || !blocks_out || P <= 0 || csum_stride < C || cap <= 0 || rows_per_rank < 0 || row0 < 0 ||
       row0 + F * N > R_total ||
       (rows_per_rank > 0 && (rows_per_rank % 2 || P % rows_per_rank)))
     return fail(VC2_ERR_ARG, "bad video_centre_blocks arguments");
   { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
   Plan p;
-  int rc = make_plan(F, N, D, dtype, &p, R_total / N);
+  int rc = make_plan(F, N, D, so.pdt, &p, R_total / N, 0, opts != nullptr);
   if (rc) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  const VcLayout lay = vc_layout(so, R_total);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ChanSet cs0 = make_chanset(p, cols, spos, C);
   if (!vc_blocks_ok(p, R_total, cs0.strict)) return VC2_OK;      // nothing to exchange: phase 2 keeps the exact means
@@ -5431,32 +5605,52 @@ int vc2_video_centre_blocks(const void* x, int64_t F, int64_t N, int64_t D, int 
                                             int(rows_per_rank), margin_depth(R_total, cs0.strict), FrameStatSrc{},
                                             (const float*)nullptr, 0));
   const int lpv = cascade_lp(R_total);
-  const int64_t nb = p.R >> lpv;                               // (at most; one more grid column for the raw edges)
-  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64), 0,
-                                            st, vflag, int(C), x, int(D), cols, spos, wsp<float>(ws, p.o_den), p.R, row0,
-                                            lpv, blocks_out, 0));
+  const int64_t nb = so.tail ? p.R >> 4 : p.R >> lpv;          // (at most -- a tail column: four sums per run of >= 64 rows; one more grid column for the raw edges)
+  {                                                             // (exchange 2b: the record and finish kernels, one profile slot)
+    ProfScope ps_(KID_VC_RECORDS, static_cast<hipStream_t>(stream));
+    VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64), 0,
+                                              st, vflag, int(C), x, int(D), cols, spos, wsp<float>(ws, p.o_den), p.R, row0,
+                                              lpv, blocks_out, 0, lay));
+  }
   return check_launch("video_centre_blocks");
+}
+int vc2_video_centre_blocks(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
+                            const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
+                            int64_t rows_per_rank, int64_t R_total, int64_t row0, void* ws, size_t ws_bytes,
+                            float* blocks_out, int cap, void* stream) {
+  return vc2_video_centre_blocks_o(x, F, N, D, dtype, cols, C, spos, csum_all, P, csum_stride, rows_per_rank, R_total, row0, ws, ws_bytes, blocks_out, cap, stream, nullptr);
 }
 
 // Rounds of exchange 2b beyond the first `cap` flagged columns (vc2.h): the records of flagged columns
 // [col_offset, col_offset + cap), the flags being those vc2_video_centre_blocks left in the workspace
-int vc2_video_centre_blocks_round(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+int vc2_video_centre_blocks_round_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
                                   int64_t C, const int32_t* spos, int64_t R_total, int64_t row0, void* ws, size_t ws_bytes,
-                                  float* blocks_out, int cap, int col_offset, void* stream) {
+                                  float* blocks_out, int cap, int col_offset, void* stream, const vc2_shard_opts* opts) {
   if (!x || !blocks_out || cap <= 0 || col_offset < 0 || row0 < 0 || row0 + F * N > R_total)
     return fail(VC2_ERR_ARG, "bad video_centre_blocks_round arguments");
   { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
   Plan p;
-  int rc = make_plan(F, N, D, dtype, &p, R_total / N);
+  int rc = make_plan(F, N, D, so.pdt, &p, R_total / N, 0, opts != nullptr);
   if (rc) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  const VcLayout lay = vc_layout(so, R_total);
   if (!vc_blocks_ok(p, R_total, make_chanset(p, cols, spos, C).strict)) return VC2_OK;
   const int lpv = cascade_lp(R_total);
-  const int64_t nb = p.R >> lpv;
-  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64), 0,
-                                            static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), x, int(D),
-                                            cols, spos, wsp<float>(ws, p.o_den), p.R, row0, lpv, blocks_out, col_offset));
+  const int64_t nb = so.tail ? p.R >> 4 : p.R >> lpv;
+  {                                                             // (exchange 2b: the record and finish kernels, one profile slot)
+    ProfScope ps_(KID_VC_RECORDS, static_cast<hipStream_t>(stream));
+    VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64), 0,
+                                              static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), x, int(D),
+                                              cols, spos, wsp<float>(ws, p.o_den), p.R, row0, lpv, blocks_out, col_offset, lay));
+  }
   return check_launch("video_centre_blocks_round");
+}
+int vc2_video_centre_blocks_round(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                  int64_t C, const int32_t* spos, int64_t R_total, int64_t row0, void* ws, size_t ws_bytes,
+                                  float* blocks_out, int cap, int col_offset, void* stream) {
+  return vc2_video_centre_blocks_round_o(x, F, N, D, dtype, cols, C, spos, R_total, row0, ws, ws_bytes, blocks_out, cap, col_offset, stream, nullptr);
 }
 
 // how many columns vc2_video_centre_blocks flagged (SYNCHRONISES the stream): the rounds the caller has to go
@@ -5477,20 +5671,32 @@ int vc2_video_centre_flagged(int64_t F, int64_t N, int64_t D, int dtype, int64_t
 // ... and the finish of one round: torch's cascade over the whole video for flagged columns [col_offset, col_offset + cap)
 // from the all-gathered records; the video centre in the workspace is corrected in place (vc2_scores_phase2_blocks with
 // world = -1 then scores with it as it stands)
+int vc2_video_centre_finish_round_o(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
+                                  int64_t R_total, void* ws, size_t ws_bytes, const float* blocks_all, int world, int cap,
+                                  int col_offset, void* stream, const vc2_shard_opts* opts) {
+  if (!blocks_all || world <= 0 || cap <= 0 || col_offset < 0) return fail(VC2_ERR_ARG, "bad video_centre_finish_round arguments");
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
+  Plan p;
+  int rc = make_plan(F, N, D, so.pdt, &p, R_total / N, 0, opts != nullptr);
+  if (rc) return rc;
+  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  const VcLayout lay = vc_layout(so, R_total);
+  if (R_total != int64_t(world) * p.R) return fail(VC2_ERR_ARG, "finish_round: R_total != world * F * N");
+  if (so.pdt != dtype) return VC2_OK;                           // (fp32 scoring: no records were written, nothing to finish)
+  {                                                             // (exchange 2b: the record and finish kernels, one profile slot)
+    ProfScope ps_(KID_VC_RECORDS, static_cast<hipStream_t>(stream));
+    VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish<DT>), dim3(unsigned(cap)), dim3(256), 0,
+                                              static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), spos,
+                                              blocks_all, world, cap, p.R, R_total, wsp<float>(ws, p.o_vc),
+                                              wsp<int>(ws, p.o_ticket) + 5, col_offset, lay));
+  }
+  return check_launch("video_centre_finish_round");
+}
 int vc2_video_centre_finish_round(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
                                   int64_t R_total, void* ws, size_t ws_bytes, const float* blocks_all, int world, int cap,
                                   int col_offset, void* stream) {
-  if (!blocks_all || world <= 0 || cap <= 0 || col_offset < 0) return fail(VC2_ERR_ARG, "bad video_centre_finish_round arguments");
-  Plan p;
-  int rc = make_plan(F, N, D, dtype, &p, R_total / N);
-  if (rc) return rc;
-  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
-  if (R_total != int64_t(world) * p.R) return fail(VC2_ERR_ARG, "finish_round: R_total != world * F * N");
-  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish<DT>), dim3(unsigned(cap)), dim3(256), 0,
-                                            static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), spos,
-                                            blocks_all, world, cap, p.R, R_total, wsp<float>(ws, p.o_vc),
-                                            wsp<int>(ws, p.o_ticket) + 5, col_offset));
-  return check_launch("video_centre_finish_round");
+  return vc2_video_centre_finish_round_o(F, N, D, dtype, C, spos, R_total, ws, ws_bytes, blocks_all, world, cap, col_offset, stream, nullptr);
 }
 
 int vc2_scores_phase2(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
@@ -5501,25 +5707,28 @@ int vc2_scores_phase2(const void* x, int64_t F, int64_t N, int64_t D, int dtype,
                                   ws_bytes, v_T, f_T, total_f32, s_f32, nullptr, 0, 0, stream);
 }
 
-int vc2_scores_phase2_blocks(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
+int vc2_scores_phase2_blocks_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
                              const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
                              int64_t rows_per_rank, int64_t R_total, void* ws, size_t ws_bytes, void* v_T, void* f_T,
-                             float* total_f32, float* s_f32, const float* blocks_all, int world, int cap, void* stream) {
+                             float* total_f32, float* s_f32, const float* blocks_all, int world, int cap, void* stream, const vc2_shard_opts* opts) {
   if (!x || !csum_all || P <= 0 || csum_stride < C || rows_per_rank < 0 ||
       (rows_per_rank > 0 && (rows_per_rank % 2 || P % rows_per_rank)))
     return fail(VC2_ERR_ARG, "bad phase-2 arguments");
   { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
   Plan p;
-  int rc = make_plan(F, N, D, dtype, &p, R_total / N);
+  int rc = make_plan(F, N, D, so.pdt, &p, R_total / N, 0, opts != nullptr);
   if (rc) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  const VcLayout lay = vc_layout(so, R_total);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ChanSet cs0 = make_chanset(p, cols, spos, C);
   const bool have_blocks = blocks_all && world > 0 && cap > 0 && vc_blocks_ok(p, R_total, cs0.strict) &&
                            R_total == int64_t(world) * p.R;
   const bool vc_final = world < 0;   // the caller ran vc2_video_centre_blocks + the finish rounds: the centre is final
   if (!have_blocks && !vc_final)     // (with blocks: vc2_video_centre_blocks already computed the means, the flags and the count)
-    VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_video_centre<DT>), dim3(unsigned(cdiv(C, 64))), dim3(64), 512 /* (replay_rows = 0: no LDS use) */, st,
+    VC2_DISPATCH_DT_PASS(p.dt,hipLaunchKernelGGL((k_video_centre<DT>), dim3(unsigned(cdiv(C, 64))), dim3(64), 512 /* (replay_rows = 0: no LDS use) */, st,
                                               csum_all, int(P), csum_stride, int(C), R_total, wsp<float>(ws, p.o_vc), x,
                                               int(D), cols, spos, wsp<float>(ws, p.o_den), cs0.strict, 0,
                                               wsp<int>(ws, p.o_ticket) + 5, (float*)nullptr, 0, (int*)nullptr,
@@ -5528,13 +5737,21 @@ int vc2_scores_phase2_blocks(const void* x, int64_t F, int64_t N, int64_t D, int
   // ticket[5] = video-centre columns whose mean lies within the replay margin of a T rounding boundary.  With the
   // all-gathered level-0 block sums (vc2_video_centre_blocks) torch's cascade is finished here for the first `cap`
   // of them; the others keep the exactly rounded mean and stay counted (vc2_select_sharded reports K_out[2]).
-  if (have_blocks)
+  if (have_blocks) {                                             // (exchange 2b: the record and finish kernels, one profile slot)
+    ProfScope ps_(KID_VC_RECORDS, static_cast<hipStream_t>(stream));
     VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish<DT>), dim3(unsigned(cap)), dim3(256), 0, st,
                                               wsp<uint8_t>(ws, p.o_mask), int(C), spos, blocks_all, world, cap,
-                                              p.R, R_total, wsp<float>(ws, p.o_vc), wsp<int>(ws, p.o_ticket) + 5, 0));
+                                              p.R, R_total, wsp<float>(ws, p.o_vc), wsp<int>(ws, p.o_ticket) + 5, 0, lay));
+  }
   float* total = total_f32 ? total_f32 : wsp<float>(ws, p.o_total);
   float* s = s_f32 ? s_f32 : wsp<float>(ws, p.o_s);
-  return launch_phase2(p, x, make_chanset(p, cols, spos, C), ws, v_T, f_T, total, s, st);
+  return launch_phase2(p, x, make_chanset(p, cols, spos, C), ws, v_T, f_T, total, s, st, so.ps.al());
+}
+int vc2_scores_phase2_blocks(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
+                             const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
+                             int64_t rows_per_rank, int64_t R_total, void* ws, size_t ws_bytes, void* v_T, void* f_T,
+                             float* total_f32, float* s_f32, const float* blocks_all, int world, int cap, void* stream) {
+  return vc2_scores_phase2_blocks_o(x, F, N, D, dtype, cols, C, spos, csum_all, P, csum_stride, rows_per_rank, R_total, ws, ws_bytes, v_T, f_T, total_f32, s_f32, blocks_all, world, cap, stream, nullptr);
 }
 
 // ---- exchange 2b for ranks with UNEQUAL row counts (vc2.h): the layout of the video over the ranks comes as a host
@@ -5544,7 +5761,7 @@ static bool vc_blocks_ok_ragged(const Plan& p, int64_t R_total, int strict) {
   return strict != 0 && at_of(p.dt) != VC2_F32 && cascade_modelled(R_total);
 }
 static int make_rank_table(const int64_t* rank_rows, int world, int rank, int64_t F, int64_t N, int64_t R_total,
-                           VcRankTable* tab) {
+                           int edge, VcRankTable* tab) {
   if (!rank_rows || world <= 0 || rank < 0 || rank >= world) return fail(VC2_ERR_ARG, "bad rank layout (world=%d, rank=%d)", world, rank);
   if (world > kVcMaxWorld)
     return fail(VC2_ERR_UNSUPPORTED, "ragged layout of %d ranks; at most %d are supported", world, kVcMaxWorld);
@@ -5559,24 +5776,27 @@ static int make_rank_table(const int64_t* rank_rows, int world, int rank, int64_
   if (sum != R_total || rank_rows[rank] != F * N)
     return fail(VC2_ERR_ARG, "rank layout: the ranks' rows sum to %lld (R_total %lld), rank %d holds %lld (F * N = %lld)",
                 (long long)sum, (long long)R_total, rank, (long long)rank_rows[rank], (long long)(F * N));
-  tab->rec = vc_rec_floats(most);
+  tab->rec = vc_rec_floats(most, edge);
   tab->world = world;
   return VC2_OK;
 }
 
-int vc2_video_centre_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+int vc2_video_centre_blocks_ragged_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
                                    int64_t C, const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
                                    int64_t rows_per_rank, int64_t R_total, const int64_t* rank_rows, int world, int rank,
-                                   void* ws, size_t ws_bytes, float* blocks_out, int cap, void* stream) {
+                                   void* ws, size_t ws_bytes, float* blocks_out, int cap, void* stream, const vc2_shard_opts* opts) {
   if (!x || !csum_all || !blocks_out || P <= 0 || csum_stride < C || cap <= 0 || rows_per_rank < 0 ||
       (rows_per_rank > 0 && (rows_per_rank % 2 || P % rows_per_rank)))
     return fail(VC2_ERR_ARG, "bad video_centre_blocks_ragged arguments");
   { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
-  VcRankTable tab;
-  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, &tab);
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
+  const VcLayout lay = vc_layout(so, R_total);
+  VcRankTable tab;                                              // (one record stride for all ranks, in this pass's layout)
+  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, lay.edge, &tab);
   if (rc) return rc;
   Plan p;
-  if ((rc = make_plan(F, N, D, dtype, &p, R_total / N))) return rc;
+  if ((rc = make_plan(F, N, D, so.pdt, &p, R_total / N, 0, opts != nullptr))) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ChanSet cs0 = make_chanset(p, cols, spos, C);
@@ -5589,80 +5809,126 @@ int vc2_video_centre_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t 
                                             int(rows_per_rank), margin_depth(R_total, cs0.strict), FrameStatSrc{},
                                             (const float*)nullptr, 0));
   const int lpv = cascade_lp(R_total);
-  const int64_t nb = p.R >> lpv;                               // (at most; one more grid column for the raw edges)
-  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks_ragged<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64),
-                                            0, st, vflag, int(C), x, int(D), cols, wsp<float>(ws, p.o_den), p.R,
-                                            tab.pre[rank], lpv, blocks_out, 0, tab.rec));
+  const int64_t nb = so.tail ? p.R >> 4 : p.R >> lpv;          // (at most -- a tail column: four sums per run of >= 64 rows; one more grid column for the raw edges)
+  {                                                             // (exchange 2b: the record and finish kernels, one profile slot)
+    ProfScope ps_(KID_VC_RECORDS, static_cast<hipStream_t>(stream));
+    VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks_ragged<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64),
+                                              0, st, vflag, int(C), x, int(D), cols, spos, wsp<float>(ws, p.o_den), p.R,
+                                              tab.pre[rank], lpv, blocks_out, 0, tab.rec, lay));
+  }
   return check_launch("video_centre_blocks_ragged");
 }
+int vc2_video_centre_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                   int64_t C, const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
+                                   int64_t rows_per_rank, int64_t R_total, const int64_t* rank_rows, int world, int rank,
+                                   void* ws, size_t ws_bytes, float* blocks_out, int cap, void* stream) {
+  return vc2_video_centre_blocks_ragged_o(x, F, N, D, dtype, cols, C, spos, csum_all, P, csum_stride, rows_per_rank, R_total, rank_rows, world, rank, ws, ws_bytes, blocks_out, cap, stream, nullptr);
+}
 
+int vc2_video_centre_blocks_round_ragged_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                         int64_t C, const int32_t* spos, int64_t R_total, const int64_t* rank_rows,
+                                         int world, int rank, void* ws, size_t ws_bytes, float* blocks_out, int cap,
+                                         int col_offset, void* stream, const vc2_shard_opts* opts) {
+  if (!x || !blocks_out || cap <= 0 || col_offset < 0) return fail(VC2_ERR_ARG, "bad video_centre_blocks_round_ragged arguments");
+  { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
+  const VcLayout lay = vc_layout(so, R_total);
+  VcRankTable tab;                                              // (one record stride for all ranks, in this pass's layout)
+  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, lay.edge, &tab);
+  if (rc) return rc;
+  Plan p;
+  if ((rc = make_plan(F, N, D, so.pdt, &p, R_total / N, 0, opts != nullptr))) return rc;
+  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  if (!vc_blocks_ok_ragged(p, R_total, make_chanset(p, cols, spos, C).strict)) return VC2_OK;
+  const int lpv = cascade_lp(R_total);
+  const int64_t nb = so.tail ? p.R >> 4 : p.R >> lpv;
+  {                                                             // (exchange 2b: the record and finish kernels, one profile slot)
+    ProfScope ps_(KID_VC_RECORDS, static_cast<hipStream_t>(stream));
+    VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks_ragged<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64),
+                                              0, static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), x,
+                                              int(D), cols, spos, wsp<float>(ws, p.o_den), p.R, tab.pre[rank], lpv, blocks_out,
+                                              col_offset, tab.rec, lay));
+  }
+  return check_launch("video_centre_blocks_round_ragged");
+}
 int vc2_video_centre_blocks_round_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
                                          int64_t C, const int32_t* spos, int64_t R_total, const int64_t* rank_rows,
                                          int world, int rank, void* ws, size_t ws_bytes, float* blocks_out, int cap,
                                          int col_offset, void* stream) {
-  if (!x || !blocks_out || cap <= 0 || col_offset < 0) return fail(VC2_ERR_ARG, "bad video_centre_blocks_round_ragged arguments");
-  { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
-  VcRankTable tab;
-  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, &tab);
-  if (rc) return rc;
-  Plan p;
-  if ((rc = make_plan(F, N, D, dtype, &p, R_total / N))) return rc;
-  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
-  if (!vc_blocks_ok_ragged(p, R_total, make_chanset(p, cols, spos, C).strict)) return VC2_OK;
-  const int lpv = cascade_lp(R_total);
-  const int64_t nb = p.R >> lpv;
-  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_blocks_ragged<DT>), dim3(unsigned(cdiv(nb, 64) + 1), unsigned(cap)), dim3(64),
-                                            0, static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), x,
-                                            int(D), cols, wsp<float>(ws, p.o_den), p.R, tab.pre[rank], lpv, blocks_out,
-                                            col_offset, tab.rec));
-  return check_launch("video_centre_blocks_round_ragged");
+  return vc2_video_centre_blocks_round_ragged_o(x, F, N, D, dtype, cols, C, spos, R_total, rank_rows, world, rank, ws, ws_bytes, blocks_out, cap, col_offset, stream, nullptr);
 }
 
+int vc2_video_centre_finish_round_ragged_o(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
+                                         int64_t R_total, const int64_t* rank_rows, int world, int rank, void* ws,
+                                         size_t ws_bytes, const float* blocks_all, int cap, int col_offset, void* stream, const vc2_shard_opts* opts) {
+  if (!blocks_all || cap <= 0 || col_offset < 0) return fail(VC2_ERR_ARG, "bad video_centre_finish_round_ragged arguments");
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
+  const VcLayout lay = vc_layout(so, R_total);
+  VcRankTable tab;                                              // (one record stride for all ranks, in this pass's layout)
+  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, lay.edge, &tab);
+  if (rc) return rc;
+  Plan p;
+  if ((rc = make_plan(F, N, D, so.pdt, &p, R_total / N, 0, opts != nullptr))) return rc;
+  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  if (so.pdt != dtype) return VC2_OK;                           // (fp32 scoring: no records were written, nothing to finish)
+  {                                                             // (exchange 2b: the record and finish kernels, one profile slot)
+    ProfScope ps_(KID_VC_RECORDS, static_cast<hipStream_t>(stream));
+    VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish_ragged<DT>), dim3(unsigned(cap)), dim3(256), 0,
+                                              static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), spos,
+                                              blocks_all, cap, tab, R_total, wsp<float>(ws, p.o_vc),
+                                              wsp<int>(ws, p.o_ticket) + 5, col_offset, lay));
+  }
+  return check_launch("video_centre_finish_round_ragged");
+}
 int vc2_video_centre_finish_round_ragged(int64_t F, int64_t N, int64_t D, int dtype, int64_t C, const int32_t* spos,
                                          int64_t R_total, const int64_t* rank_rows, int world, int rank, void* ws,
                                          size_t ws_bytes, const float* blocks_all, int cap, int col_offset, void* stream) {
-  if (!blocks_all || cap <= 0 || col_offset < 0) return fail(VC2_ERR_ARG, "bad video_centre_finish_round_ragged arguments");
-  VcRankTable tab;
-  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, &tab);
-  if (rc) return rc;
-  Plan p;
-  if ((rc = make_plan(F, N, D, dtype, &p, R_total / N))) return rc;
-  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
-  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish_ragged<DT>), dim3(unsigned(cap)), dim3(256), 0,
-                                            static_cast<hipStream_t>(stream), wsp<uint8_t>(ws, p.o_mask), int(C), spos,
-                                            blocks_all, cap, tab, R_total, wsp<float>(ws, p.o_vc),
-                                            wsp<int>(ws, p.o_ticket) + 5, col_offset));
-  return check_launch("video_centre_finish_round_ragged");
+  return vc2_video_centre_finish_round_ragged_o(F, N, D, dtype, C, spos, R_total, rank_rows, world, rank, ws, ws_bytes, blocks_all, cap, col_offset, stream, nullptr);
 }
 
-int vc2_scores_phase2_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+int vc2_scores_phase2_blocks_ragged_o(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
                                     int64_t C, const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
                                     int64_t rows_per_rank, int64_t R_total, const int64_t* rank_rows, int world, int rank,
                                     void* ws, size_t ws_bytes, void* v_T, void* f_T, float* total_f32, float* s_f32,
-                                    const float* blocks_all, int cap, void* stream) {
+                                    const float* blocks_all, int cap, void* stream, const vc2_shard_opts* opts) {
   if (!x || !csum_all || !blocks_all || cap <= 0 || P <= 0 || csum_stride < C || rows_per_rank < 0 ||
       (rows_per_rank > 0 && (rows_per_rank % 2 || P % rows_per_rank)))
     return fail(VC2_ERR_ARG, "bad phase-2 arguments");
   { int rcc = check_cols(cols, C, D); if (rcc) return rcc; }
-  VcRankTable tab;
-  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, &tab);
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, C, &so); if (rco) return rco; }
+  const VcLayout lay = vc_layout(so, R_total);
+  VcRankTable tab;                                              // (one record stride for all ranks, in this pass's layout)
+  int rc = make_rank_table(rank_rows, world, rank, F, N, R_total, lay.edge, &tab);
   if (rc) return rc;
   Plan p;
-  if ((rc = make_plan(F, N, D, dtype, &p, R_total / N))) return rc;
+  if ((rc = make_plan(F, N, D, so.pdt, &p, R_total / N, 0, opts != nullptr))) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const ChanSet cs0 = make_chanset(p, cols, spos, C);
   // the records exist (vc2_video_centre_blocks_ragged wrote them) exactly when that call found the replay applicable;
   // otherwise this is vc2_scores_phase2: exact means, counted
   if (!vc_blocks_ok_ragged(p, R_total, cs0.strict))
-    return vc2_scores_phase2_blocks(x, F, N, D, dtype, cols, C, spos, csum_all, P, csum_stride, rows_per_rank, R_total, ws,
-                                    ws_bytes, v_T, f_T, total_f32, s_f32, nullptr, 0, 0, stream);
-  VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish_ragged<DT>), dim3(unsigned(cap)), dim3(256), 0, st,
-                                            wsp<uint8_t>(ws, p.o_mask), int(C), spos, blocks_all, cap, tab, R_total,
-                                            wsp<float>(ws, p.o_vc), wsp<int>(ws, p.o_ticket) + 5, 0));
+    return vc2_scores_phase2_blocks_o(x, F, N, D, dtype, cols, C, spos, csum_all, P, csum_stride, rows_per_rank, R_total, ws,
+                                      ws_bytes, v_T, f_T, total_f32, s_f32, nullptr, 0, 0, stream, opts);
+  {                                                             // (exchange 2b: the record and finish kernels, one profile slot)
+    ProfScope ps_(KID_VC_RECORDS, static_cast<hipStream_t>(stream));
+    VC2_DISPATCH_DT(dtype, hipLaunchKernelGGL((k_vc_finish_ragged<DT>), dim3(unsigned(cap)), dim3(256), 0, st,
+                                              wsp<uint8_t>(ws, p.o_mask), int(C), spos, blocks_all, cap, tab, R_total,
+                                              wsp<float>(ws, p.o_vc), wsp<int>(ws, p.o_ticket) + 5, 0, lay));
+  }
   float* total = total_f32 ? total_f32 : wsp<float>(ws, p.o_total);
   float* s = s_f32 ? s_f32 : wsp<float>(ws, p.o_s);
-  return launch_phase2(p, x, cs0, ws, v_T, f_T, total, s, st);
+  return launch_phase2(p, x, cs0, ws, v_T, f_T, total, s, st, so.ps.al());
+}
+int vc2_scores_phase2_blocks_ragged(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols,
+                                    int64_t C, const int32_t* spos, const double* csum_all, int64_t P, int64_t csum_stride,
+                                    int64_t rows_per_rank, int64_t R_total, const int64_t* rank_rows, int world, int rank,
+                                    void* ws, size_t ws_bytes, void* v_T, void* f_T, float* total_f32, float* s_f32,
+                                    const float* blocks_all, int cap, void* stream) {
+  return vc2_scores_phase2_blocks_ragged_o(x, F, N, D, dtype, cols, C, spos, csum_all, P, csum_stride, rows_per_rank, R_total, rank_rows, world, rank, ws, ws_bytes, v_T, f_T, total_f32, s_f32, blocks_all, cap, stream, nullptr);
 }
 
 int vc2_scores(const void* x, int64_t F, int64_t N, int64_t D, int dtype, const int32_t* cols, int64_t C,
@@ -5955,10 +6221,6 @@ int vc2_compress_ex2(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
                           idx_out, cap, ks, K_out, v_T, f_T, tail, tail_rows, flags, K_host, nullptr, stream);
 }
 
-// the reference's hyper-parameters: int(D * 0.5) channels (vidcom2.py:41), temp 0.01 (:66), alphas 2^-3 .. 2^1 (:54)
-constexpr double kRefTemp = 0.01;
-constexpr double kRefAlphas[5] = {0.125, 0.25, 0.5, 1.0, 2.0};
-
 int vc2_compress_ex3(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale, int map_mode,
                      int64_t grid_h, const void* gather_src, int64_t gather_rows, void* ws, size_t ws_bytes,
                      void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
@@ -5983,31 +6245,11 @@ int vc2_compress_ex4(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   const int adt = at_of(pdt);                             // the kernels that round and read no row take this dtype
   // the pass's hyper-parameters: checked before anything else so that nothing is enqueued on a bad set.  A set equal to the
   // reference's is the default pass: the same kernel instantiations as params == NULL.
-  int64_t kc = int64_t(double(D) * 0.5);                  // int(x.shape[-1] * ratio), vidcom2.py:41
-  double temp = kRefTemp;
-  MsgAlphas alphas;
-  const MsgAlphas* al = nullptr;
-  if (params) {
-    if (params->channels < 1 || params->channels > D)
-      return fail(VC2_ERR_ARG, "params: %lld channels of %lld", (long long)params->channels, (long long)D);
-    if (!(params->temp > 0.0) || !std::isfinite(params->temp)) return fail(VC2_ERR_ARG, "params: temp must be finite and > 0");
-    if (params->n_alphas < 1) return fail(VC2_ERR_ARG, "params: no Gaussian scales");
-    if (params->n_alphas > kMaxAlphas) return fail(VC2_ERR_UNSUPPORTED, "params: more than %d Gaussian scales", kMaxAlphas);
-    for (int i = 0; i < params->n_alphas; ++i)
-      if (!(params->alphas[i] > 0.0) || !std::isfinite(params->alphas[i]))
-        return fail(VC2_ERR_ARG, "params: Gaussian scale %d must be finite and > 0", i);
-    if (params->channels > 4096) return fail(VC2_ERR_UNSUPPORTED, "params: more than 4096 scored channels");
-    kc = params->channels;
-    temp = params->temp;
-    bool ref_scales = params->n_alphas == 5;
-    for (int i = 0; ref_scales && i < 5; ++i) ref_scales = params->alphas[i] == kRefAlphas[i];
-    if (!ref_scales) {
-      alphas.n = params->n_alphas;
-      for (int i = 0; i < kMaxAlphas; ++i)                 // python: -d / (2 * a), scalar -> fp32
-        alphas.two_a[i] = i < params->n_alphas ? float(2.0 * params->alphas[i]) : 1.0f;
-      al = &alphas;
-    }
-  }
+  PassSet pset;
+  { int rcp = check_pass_params(params, D, &pset); if (rcp) return rcp; }
+  const int64_t kc = pset.kc;
+  const double temp = pset.temp;
+  const MsgAlphas* al = pset.al();
   if (tail_rows < 0 || (tail_rows > 0 && !tail)) return fail(VC2_ERR_ARG, "tail_rows without tail");
   if (N > 8192) return fail(VC2_ERR_UNSUPPORTED, "N=%lld > 8192 tokens per frame", (long long)N);
   if (map_mode == VC2_MAP_GRID_VID && (grid_h <= 0 || grid_h * grid_h != N))
@@ -6107,17 +6349,19 @@ int vc2_compress_ex4(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
   return rc;
 }
 
-int vc2_select_sharded(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t f0,
+int vc2_select_sharded_o(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t f0,
                        int64_t F_local, int64_t N, int64_t D, double base_scale, int dtype, void* ws,
                        size_t ws_bytes, int64_t* ks, int64_t* idx_out, int64_t cap, int64_t* K_out,
-                       const void* gather_src, void* out_rows, void* stream) {
+                       const void* gather_src, void* out_rows, void* stream, const vc2_shard_opts* opts) {
   if (!total_f32 || !s_all_f32 || !ks || !idx_out || !K_out) return fail(VC2_ERR_ARG, "null pointer");
   if (F_total <= 0 || F_local <= 0 || f0 < 0 || f0 + F_local > F_total || F_total > kMaxFramesTotal)
     return fail(VC2_ERR_ARG, "bad frame range [%lld, %lld) of %lld", (long long)f0, (long long)(f0 + F_local),
                 (long long)F_total);
   if (N > 8192) return fail(VC2_ERR_UNSUPPORTED, "N=%lld > 8192 tokens per frame", (long long)N);
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, 0, &so); if (rco) return rco; }
   Plan p;
-  int rc = make_plan(F_local, N, D, dtype, &p, F_total);
+  int rc = make_plan(F_local, N, D, so.pdt, &p, F_total, 0, opts != nullptr);
   if (rc) return rc;
   if ((rc = need_ws(p, ws, ws_bytes))) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -6125,13 +6369,13 @@ int vc2_select_sharded(const float* total_f32, const float* s_all_f32, int64_t F
   // budgets over ALL frames of the video (softmax + mean are global, vidcom2.py:66-67), selection only for this
   // rank's frames [f0, f0 + F_local)
   if (F_total <= kFusedScalesMaxF) {
-    rc = launch_select(dtype, total_f32, F_total, f0, F_local, N, VC2_MAP_LINEAR, 0, ks, wsp<int64_t>(ws, p.o_offs),
-                       idx_out, cap, K_out, BudgetSrc{nullptr, nullptr, 0, s_all_f32, base_scale, 0.01, nullptr}, st);
+    rc = launch_select(at_of(so.pdt), total_f32, F_total, f0, F_local, N, VC2_MAP_LINEAR, 0, ks, wsp<int64_t>(ws, p.o_offs),
+                       idx_out, cap, K_out, BudgetSrc{nullptr, nullptr, 0, s_all_f32, base_scale, so.ps.temp, nullptr}, st);
   } else {
-    if ((rc = launch_scales(dtype, s_all_f32, F_total, base_scale, 0.01, wsp<float>(ws, p.o_zbuf), scales, nullptr, st)))
+    if ((rc = launch_scales(at_of(so.pdt), s_all_f32, F_total, base_scale, so.ps.temp, wsp<float>(ws, p.o_zbuf), scales, nullptr, st)))
       return rc;
-    rc = launch_select(dtype, total_f32, F_total, f0, F_local, N, VC2_MAP_LINEAR, 0, ks, wsp<int64_t>(ws, p.o_offs),
-                       idx_out, cap, K_out, BudgetSrc{scales, nullptr, 0, nullptr, base_scale, 0.01, nullptr}, st);
+    rc = launch_select(at_of(so.pdt), total_f32, F_total, f0, F_local, N, VC2_MAP_LINEAR, 0, ks, wsp<int64_t>(ws, p.o_offs),
+                       idx_out, cap, K_out, BudgetSrc{scales, nullptr, 0, nullptr, base_scale, so.ps.temp, nullptr}, st);
   }
   if (rc) return rc;
   {   // K_out[2] = number of video-centre columns left at the exactly rounded mean (see vc2_scores_phase2)
@@ -6142,6 +6386,12 @@ int vc2_select_sharded(const float* total_f32, const float* s_all_f32, int64_t F
   if (out_rows && gather_src)
     rc = launch_gather_rows(gather_src, F_local * N, D, p.ES, idx_out, K_out, cap, out_rows, st);
   return rc;
+}
+int vc2_select_sharded(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t f0,
+                       int64_t F_local, int64_t N, int64_t D, double base_scale, int dtype, void* ws,
+                       size_t ws_bytes, int64_t* ks, int64_t* idx_out, int64_t cap, int64_t* K_out,
+                       const void* gather_src, void* out_rows, void* stream) {
+  return vc2_select_sharded_o(total_f32, s_all_f32, F_total, f0, F_local, N, D, base_scale, dtype, ws, ws_bytes, ks, idx_out, cap, K_out, gather_src, out_rows, stream, nullptr);
 }
 
 int vc2_multi_scale_gaussian(const void* x, int64_t F, int64_t N, int64_t C, int dtype, const void* centre,

@@ -87,6 +87,20 @@ def compact_rows(gathered: torch.Tensor, index: torch.Tensor, out: Optional[torc
     return torch.index_select(flat, 0, index) if out is None else torch.index_select(flat, 0, index, out=out)
 
 
+class _CShardOpts(ctypes.Structure):
+    """include/vc2.h: vc2_shard_opts."""
+    _fields_ = [("params", ctypes.c_void_p), ("score_dtype", ctypes.c_int32), ("tail_records", ctypes.c_int32)]
+
+
+VC_EDGE, VC_EDGE_TAIL = 64, 256      # raw edge values per side of an exchange-2b record: narrow / wide layout (vc2.h)
+
+
+def tail_columns(C: int) -> int:
+    """Video-centre columns torch sums with row_sum's four interleaved chains: the last C % 32 in torch.topk's order
+    (C % 4 when C < 8)."""
+    return int(C) % (32 if C >= 8 else 4)
+
+
 @dataclass
 class ShardResult:
     rows: Optional[torch.Tensor]     # [K_local, D] kept rows of this rank's frames
@@ -100,10 +114,18 @@ class HipStages:
     """The five shard-local stages on the HIP kernels (include/vc2.h 'frame-sharded building blocks')."""
 
     def __init__(self, F: int, N: int, D: int, dtype, device, base_scale: float, gather: bool = True,
-                 vc_cap: int = 64, frames=None, rank: int = 0):
+                 vc_cap: int = 64, frames=None, rank: int = 0, params=None, score_dtype=None):
         """frames / rank: the layout of the video over the ranks (every rank's frame count, this rank's number).  None,
         or equal counts: the equal-shard pass (F_total = world * F, set by ShardedCompressor).  Unequal counts: the buffers
-        that take part in an exchange are sized for the largest rank and exchange 2b goes through the ragged entry points."""
+        that take part in an exchange are sized for the largest rank and exchange 2b goes through the ragged entry points.
+        params (a PassParams) / score_dtype: as in `compress`.  None, a set equal to the reference's defaults and
+        score_dtype == dtype are the plain pass: the same entry points with the same arguments.  Bad sets raise here, as
+        CompressPlan raises them (ValueError / NotImplementedError), before any collective."""
+        from .vidcom2 import _c_params, _norm_params, _norm_score_dtype
+        self.params = _norm_params(params)
+        # fp32 scoring of bf16 / fp16 rows: 16-bit loads, fp32 variances, scores and selection; no "torch order" replay
+        self.score32 = _norm_score_dtype(score_dtype, dtype) is not None
+        self._cparams = _c_params(self.params, D)              # (raises for a channel count of 0 or above the sweeps' limit)
         self.F, self.N, self.D, self.dtype, self.device, self.base = F, N, D, dtype, torch.device(device), base_scale
         self.code = DTYPE_CODE[dtype]
         L = lib()
@@ -120,7 +142,7 @@ class HipStages:
         # power of two that divides every rank's count
         self.bf = stat_block_frames(self.frames if self.ragged else [F])
         self.stats = torch.empty((F // self.bf, 2, D), dtype=torch.float64, device=self.device)
-        self.C = int(D * 0.5)                                   # int(x.shape[-1] * ratio), vidcom2.py:41
+        self.C = int(self._cparams.channels) if self._cparams is not None else int(D * 0.5)   # int(x.shape[-1] * ratio), vidcom2.py:41
         # exchange 2: per group of 16 frames the sums of x^ and, behind them, the groups' bounds of sum |x^|.  Unequal
         # shards: k_video_centre reads every rank's message as [half sums | half bounds], so a rank with fewer groups
         # than the largest pads INSIDE each half (zero rows: they change neither the sums nor the bounds)
@@ -146,11 +168,20 @@ class HipStages:
         self.kout = torch.zeros(4, dtype=torch.int64, device=self.device)     # K, capacity overflow, fragile centre columns
         # exchange 2b (video-centre replay): level-0 block sums of this rank's rows for up to vc_cap flagged columns
         self.vc_cap = int(vc_cap)                             # flagged columns whose blocks one exchange carries
-        self.vc_replay = dtype != torch.float32
+        self.vc_replay = dtype != torch.float32 and not self.score32
         # per flagged column: 64 + 64 raw edge values and the sums of this rank's complete blocks (include/vc2.h)
         # (unequal shards: every rank's records have the stride of the rank with the most rows)
-        self.blocks = torch.zeros((self.vc_cap, 129 + (max(self.frames) if self.ragged else F) * N // 16),
+        # The C % 32 tail columns (row_sum's four interleaved chains) need the WIDE layout: 256 + 256 raw edge values and
+        # four sums per complete run; then every column of the pass, plain ones included, is exchanged in it
+        self.vc_tail = self.vc_replay and tail_columns(self.C) > 0
+        self.vc_edge = VC_EDGE_TAIL if self.vc_tail else VC_EDGE
+        self.blocks = torch.zeros((self.vc_cap, 2 * self.vc_edge + 1 + (max(self.frames) if self.ragged else F) * N // 16),
                                   dtype=torch.float32, device=self.device)
+        # the options of the `_o` entry points; None: the plain symbols, today's calls
+        self._opts = None
+        if self._cparams is not None or self.vc_tail or self.score32:
+            self._opts = _CShardOpts(ctypes.addressof(self._cparams) if self._cparams is not None else None,
+                                     DTYPE_CODE[torch.float32] if self.score32 else self.code, 1 if self.vc_tail else 0)
         self.rows = torch.empty((self.cap, D), dtype=dtype, device=self.device) if gather else None
 
         # device pointers of the fixed buffers, resolved once: the per-pass host work is five C calls plus
@@ -160,6 +191,13 @@ class HipStages:
                                                      "spos", "total", "s", "idx", "ks", "kout", "rows", "blocks",
                                                      "_csum_raw")}
         self._ws_n = self.ws.numel()
+
+    def _call(self, name: str, *args):
+        """The entry point `name`, or -- a pass with options -- its `_o` form with them as the trailing argument."""
+        if self._opts is None:
+            check(getattr(self._L, name)(*args), name)
+        else:
+            check(getattr(self._L, name + "_o")(*args, ctypes.byref(self._opts)), name + "_o")
 
     def _st(self):
         return stream_ptr(self.device)
@@ -172,14 +210,16 @@ class HipStages:
 
     def chan_stats(self, x):
         p = self._p
-        check(self._L.vc2_chan_stats(ptr(x), self.F, self.N, self.D, self.code, self.F_total, self.bf, p["ws"],
-                                     self._ws_n, p["stats"], self._st()), "vc2_chan_stats")
+        self._call("vc2_chan_stats", ptr(x), self.F, self.N, self.D, self.code, self.F_total, self.bf, p["ws"],
+                   self._ws_n, p["stats"], self._st())
         return self.stats
 
     def select_channels(self, stats_all, R_total):
         p, st = self._p, self._st()
         blocks = stats_all.reshape(-1, 2, self.D)               # [world * nb, 2, D], rank order = frame order
-        check(self._L.vc2_chan_var_from_stats(ptr(blocks), blocks.shape[0], self.bf * self.N, R_total, self.D, self.code,
+        # (the variance is rounded to the SCORING dtype: fp32 ones go through vc2_chan_select's 64-bit selection words)
+        check(self._L.vc2_chan_var_from_stats(ptr(blocks), blocks.shape[0], self.bf * self.N, R_total, self.D,
+                                              DTYPE_CODE[torch.float32] if self.score32 else self.code,
                                               None, p["var_f32"], st), "vc2_chan_var_from_stats")
         # the channel SET now; torch.topk's channel ORDER (needed only by the fix-up kernels of phase 1) is
         # replayed from `perm` by a rider workgroup of sweep 2 inside vc2_scores_phase1
@@ -188,10 +228,8 @@ class HipStages:
 
     def phase1(self, x):
         p = self._p
-        check(self._L.vc2_scores_phase1(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
-                                        p["perm"], p["var_f32"], self.F_total, p["ws"], self._ws_n, p["_csum_raw"],
-                                        self._st()),
-              "vc2_scores_phase1")
+        self._call("vc2_scores_phase1", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
+                   p["perm"], p["var_f32"], self.F_total, p["ws"], self._ws_n, p["_csum_raw"], self._st())
         if self._G != self._Gmax:                               # fewer groups than the largest rank: pad inside each half
             self.csum[: self._G].copy_(self._csum_raw[: self._G])
             self.csum[self._Gmax: self._Gmax + self._G].copy_(self._csum_raw[self._G:])
@@ -209,19 +247,16 @@ class HipStages:
         p = self._p
         parts = csum_all.reshape(-1, csum_all.shape[-1])
         if self.ragged:
-            check(self._L.vc2_video_centre_blocks_ragged(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
-                                                         p["spos"], ptr(parts), parts.shape[0], parts.shape[1],
-                                                         self.csum.shape[0], R_total, self._rank_rows, len(self.frames),
-                                                         self.rank, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
-                                                         self._st()), "vc2_video_centre_blocks_ragged")
+            self._call("vc2_video_centre_blocks_ragged", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
+                       p["spos"], ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total,
+                       self._rank_rows, len(self.frames), self.rank, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
+                       self._st())
             return self.blocks
         if R_total % Rl != 0:
             return None
-        check(self._L.vc2_video_centre_blocks(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
-                                              ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total,
-                                              int(f0) * self.N, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
-                                              self._st()),
-              "vc2_video_centre_blocks")
+        self._call("vc2_video_centre_blocks", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
+                   ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total, int(f0) * self.N, p["ws"],
+                   self._ws_n, p["blocks"], self.vc_cap, self._st())
         return self.blocks
 
     def flagged_columns(self) -> int:
@@ -240,28 +275,23 @@ class HipStages:
     def vc_blocks_round(self, x, R_total, f0, col_offset):
         p = self._p
         if self.ragged:
-            check(self._L.vc2_video_centre_blocks_round_ragged(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
-                                                               p["spos"], R_total, self._rank_rows, len(self.frames),
-                                                               self.rank, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
-                                                               int(col_offset), self._st()),
-                  "vc2_video_centre_blocks_round_ragged")
+            self._call("vc2_video_centre_blocks_round_ragged", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
+                       p["spos"], R_total, self._rank_rows, len(self.frames), self.rank, p["ws"], self._ws_n, p["blocks"],
+                       self.vc_cap, int(col_offset), self._st())
             return self.blocks
-        check(self._L.vc2_video_centre_blocks_round(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
-                                                    R_total, int(f0) * self.N, p["ws"], self._ws_n, p["blocks"], self.vc_cap,
-                                                    int(col_offset), self._st()), "vc2_video_centre_blocks_round")
+        self._call("vc2_video_centre_blocks_round", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
+                   R_total, int(f0) * self.N, p["ws"], self._ws_n, p["blocks"], self.vc_cap, int(col_offset), self._st())
         return self.blocks
 
     def vc_finish_round(self, R_total, blocks_all, col_offset):
         p = self._p
         if self.ragged:
-            check(self._L.vc2_video_centre_finish_round_ragged(self.F, self.N, self.D, self.code, self.C, p["spos"], R_total,
-                                                               self._rank_rows, len(self.frames), self.rank, p["ws"],
-                                                               self._ws_n, ptr(blocks_all), self.vc_cap, int(col_offset),
-                                                               self._st()), "vc2_video_centre_finish_round_ragged")
+            self._call("vc2_video_centre_finish_round_ragged", self.F, self.N, self.D, self.code, self.C, p["spos"], R_total,
+                       self._rank_rows, len(self.frames), self.rank, p["ws"], self._ws_n, ptr(blocks_all), self.vc_cap,
+                       int(col_offset), self._st())
             return
-        check(self._L.vc2_video_centre_finish_round(self.F, self.N, self.D, self.code, self.C, p["spos"], R_total, p["ws"],
-                                                    self._ws_n, ptr(blocks_all), int(blocks_all.shape[0]), self.vc_cap,
-                                                    int(col_offset), self._st()), "vc2_video_centre_finish_round")
+        self._call("vc2_video_centre_finish_round", self.F, self.N, self.D, self.code, self.C, p["spos"], R_total, p["ws"],
+                   self._ws_n, ptr(blocks_all), int(blocks_all.shape[0]), self.vc_cap, int(col_offset), self._st())
 
     def phase2(self, x, csum_all, R_total, blocks_all=None, vc_final=False):
         """vc_final: the video centre in the workspace is final (vc_blocks + vc_finish_round rounds): sweep 3 only."""
@@ -271,26 +301,21 @@ class HipStages:
         if vc_final:
             blocks_all = None
         if self.ragged and blocks_all is not None:
-            check(self._L.vc2_scores_phase2_blocks_ragged(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
-                                                          p["spos"], ptr(parts), parts.shape[0], parts.shape[1],
-                                                          self.csum.shape[0], R_total, self._rank_rows, len(self.frames),
-                                                          self.rank, p["ws"], self._ws_n, None, None, p["total"], p["s"],
-                                                          ptr(blocks_all), self.vc_cap, self._st()),
-                  "vc2_scores_phase2_blocks_ragged")
+            self._call("vc2_scores_phase2_blocks_ragged", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
+                       p["spos"], ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total, self._rank_rows,
+                       len(self.frames), self.rank, p["ws"], self._ws_n, None, None, p["total"], p["s"], ptr(blocks_all),
+                       self.vc_cap, self._st())
             return self.s
-        check(self._L.vc2_scores_phase2_blocks(ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
-                                               ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total,
-                                               p["ws"], self._ws_n, None, None, p["total"], p["s"],
-                                               ptr(blocks_all) if blocks_all is not None else None, world, self.vc_cap,
-                                               self._st()), "vc2_scores_phase2")
+        self._call("vc2_scores_phase2_blocks", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
+                   ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total, p["ws"], self._ws_n, None, None,
+                   p["total"], p["s"], ptr(blocks_all) if blocks_all is not None else None, world, self.vc_cap, self._st())
         return self.s
 
     def select(self, x, s_all, f0):
         p = self._p
-        check(self._L.vc2_select_sharded(p["total"], ptr(s_all), s_all.numel(), f0, self.F, self.N, self.D,
-                                         float(self.base), self.code, p["ws"], self._ws_n, p["ks"], p["idx"], self.cap,
-                                         p["kout"], ptr(x if self.rows is not None else None), p["rows"], self._st()),
-              "vc2_select_sharded")
+        self._call("vc2_select_sharded", p["total"], ptr(s_all), s_all.numel(), f0, self.F, self.N, self.D,
+                   float(self.base), self.code, p["ws"], self._ws_n, p["ks"], p["idx"], self.cap, p["kout"],
+                   ptr(x if self.rows is not None else None), p["rows"], self._st())
 
     def result(self, f0):
         K, overflow, vc_fragile, _ = self.kout.tolist()     # the path's single host sync
@@ -302,7 +327,7 @@ class HipStages:
             import warnings
             warnings.warn(f"vidcom2_amd (frame-sharded pass): {vc_fragile} video-centre value(s) lie within the replay margin "
                           "of a rounding boundary and could not be replayed across ranks "
-                          f"(more than {self.vc_cap} such columns in a mode that does not go in rounds, or a channel count that is not a multiple of 32); they keep "
+                          f"(more than {self.vc_cap} such columns in a mode that does not go in rounds); they keep "
                           "the exactly rounded mean, the reference's fp32 summation order could round the other way.",
                           RuntimeWarning, stacklevel=2)
         li = self.idx[:K]
@@ -332,8 +357,11 @@ class ShardedCompressor:
     phase2 returns [F_local] and select takes the compacted [F_total]."""
 
     def __init__(self, F_local: int, N: int, D: int, dtype, device, base_scale: float = 0.25, group=None,
-                 stages=None, gather: bool = True, always_collective: bool = False):
-        """always_collective: issue the all-gathers even at world size 1 (a process group must be initialised) -- the
+                 stages=None, gather: bool = True, always_collective: bool = False, params=None, score_dtype=None):
+        """params (a PassParams) / score_dtype: as in `compress`; every rank must pass the same (checked here, with the
+        geometry).  Defaults, a set equal to them and score_dtype == dtype are the plain pass.  With `stages=` they are only
+        checked across the ranks: the injected object computes what it was built for.
+        always_collective: issue the all-gathers even at world size 1 (a process group must be initialised) -- the
         only way to put the RCCL exchanges themselves under test on a single-GPU box."""
         self.group = group
         self.always_collective = bool(always_collective)
@@ -344,14 +372,23 @@ class ShardedCompressor:
         if self.F < 1:
             raise ValueError(f"ShardedCompressor: a rank needs at least one frame (got {F_local})")
         self.frames = [self.F] * self.world
+        # what the built-in stages would refuse is refused before any collective (an injected stage object: its own business)
+        from .vidcom2 import _c_params, _norm_params, _norm_score_dtype
+        self.params = _norm_params(params)
+        self.score_dtype = _norm_score_dtype(score_dtype, dtype) if isinstance(dtype, torch.dtype) else score_dtype
+        if stages is None:
+            _c_params(self.params, self.D)
         if self.world > 1:
             # the ranks may bring different numbers of frames, but one frame geometry and one dtype: say so instead of
             # hanging in a mismatched collective
             fl = [None] * self.world
-            dist.all_gather_object(fl, (self.F, self.N, self.D, str(dtype)), group=group)
-            if any(t[1:] != fl[0][1:] for t in fl) or any(t[0] < 1 for t in fl):
+            dist.all_gather_object(fl, (self.F, self.N, self.D, str(dtype), self.params, str(self.score_dtype)), group=group)
+            if any(t[1:4] != fl[0][1:4] for t in fl) or any(t[0] < 1 for t in fl):
                 raise ValueError("ShardedCompressor: every rank must hold at least one frame and the same (tokens per "
-                                 f"frame, width, dtype); got (frames, tokens per frame, width, dtype) = {fl}")
+                                 f"frame, width, dtype); got (frames, tokens per frame, width, dtype) = {[t[:4] for t in fl]}")
+            if any(t[4:] != fl[0][4:] for t in fl):
+                raise ValueError("ShardedCompressor: every rank must pass the same params and score_dtype; got "
+                                 f"{[t[4:] for t in fl]}")
             self.frames = [int(t[0]) for t in fl]
         self.ragged = len(set(self.frames)) > 1
         self.F_total = sum(self.frames)
@@ -360,9 +397,10 @@ class ShardedCompressor:
             self.stages = stages
         elif self.ragged:
             self.stages = HipStages(self.F, self.N, self.D, dtype, device, base_scale, gather, frames=self.frames,
-                                    rank=self.rank)
+                                    rank=self.rank, params=self.params, score_dtype=score_dtype)
         else:
-            self.stages = HipStages(self.F, self.N, self.D, dtype, device, base_scale, gather)
+            self.stages = HipStages(self.F, self.N, self.D, dtype, device, base_scale, gather, params=self.params,
+                                    score_dtype=score_dtype)
         if self.ragged:
             # the stage object has to cut its partials for THIS layout (stat blocks, padded group sums, record stride)
             if not callable(getattr(self.stages, "set_layout", None)):
@@ -461,7 +499,7 @@ class ShardedCompressor:
                     blocks = st.vc_blocks_round(x_local, R_total, self.f0, j0)
                 st.vc_finish_round(R_total, self._gather("blocks", blocks), j0)
             s_loc = st.phase2(x_local, csum_all, R_total, vc_final=True)
-        elif blocks is not None:                                                 # exchange 2b: [W, vc_cap, 129 + R_local/16] fp32
+        elif blocks is not None:                                                 # exchange 2b: [W, vc_cap, 129 (513: wide layout) + R_local/16] fp32
             s_loc = st.phase2(x_local, csum_all, R_total, self._gather("blocks", blocks))
         else:
             s_loc = st.phase2(x_local, csum_all, R_total)
