@@ -162,6 +162,14 @@ int vc2_map_indices(const int64_t* local_idx, const int64_t* ks, const int64_t* 
 int vc2_gather_rows(const void* src, int64_t src_rows, int64_t D, int dtype, const int64_t* idx,
                     const int64_t* K_dev, int64_t cap, void* dst, void* stream);
 
+/* vidcom2.py:93-96, :105-115  img_feat[_map_grid_vid(...)] without img_feat: idx[] holds indices into the
+ * [F*h*(h+1), D] stream LLaVA-Video's add_token_per_grid builds (every grid row of every frame followed by the
+ * image_newline embedding); out[j,:] = src[f*h*h + r*h + c,:] for g = idx[j] = f*h*(h+1) + r*(h+1) + c with c < h, and
+ * the [D] vector `newline` for c == h; j < min(n_dev[0], n_max) (n_dev NULL: n_max).  src = the scored tensor
+ * T[F*h*h, D]; the stream is never built.  An index outside [0, F*h*(h+1)) is skipped.  A null newline: VC2_ERR_ARG. */
+int vc2_gather_rows_grid(const void* src, int64_t F, int64_t h, int64_t D, int dtype, const int64_t* idx,
+                         const int64_t* n_dev, int64_t n_max, const void* newline, void* out, void* stream);
+
 /* ---- one-shot hot path -------------------------------------------------------------- */
 
 /* vidcom2.py:15-36  vidcom2_compression for the "linear" mapper (llava_ov / qwen*), and for
@@ -259,6 +267,20 @@ int vc2_compress_ex4(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
                      void* ws, size_t ws_bytes, void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks,
                      int64_t* K_out, void* v_T, void* f_T, const void* tail, int64_t tail_rows, int flags,
                      int64_t* K_host, const vc2_pass_params* params, int score_dtype, void* stream);
+
+/* vc2_compress_ex4 with the newline vector of the grid mapping (vidcom2.py:93-96, :105-115; models/llava.py:118-127):
+ * newline == NULL is exactly vc2_compress_ex4 (which forwards here).  newline = T[D] (the model's image_newline, in `dtype`)
+ * requires map_mode == VC2_MAP_GRID_VID (VC2_ERR_ARG otherwise, as for N != grid_h^2): gather_src / gather_rows are then
+ * ignored and the gather launch reads the kept rows from x itself and the newline rows from the vector, as
+ * vc2_gather_rows_grid does -- out_rows holds the bits of img_feat[idx_out] for the img_feat add_token_per_grid would have
+ * built.  idx_out stays in the stream's index space, K_out[0] still counts the F * grid_h newline rows, cap is unchanged.
+ * The newline pointer needs no alignment (a misaligned one takes the scalar copy). */
+int vc2_compress_ex5(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale,
+                     int map_mode, int64_t grid_h, const void* gather_src, int64_t gather_rows,
+                     void* ws, size_t ws_bytes, void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks,
+                     int64_t* K_out, void* v_T, void* f_T, const void* tail, int64_t tail_rows, int flags,
+                     int64_t* K_host, const vc2_pass_params* params, int score_dtype, const void* newline,
+                     void* stream);
 
 /* ---- upstream fusion: LLaVA's get_2dPool (llava/model/llava_arch.py:171-190) + sweep 1 -------
  * xin T[F, H*W, D] (the projector output, token-major) -> x_out T[F, h*w, D] = its 2x2 pool, and the sweep-1

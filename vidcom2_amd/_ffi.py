@@ -35,6 +35,7 @@ _SIGNATURES = {
     "vc2_select": [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i64, _vp, _sz, _vp, _vp, _vp, _i64, _vp, _vp],
     "vc2_map_indices": [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp],
     "vc2_gather_rows": [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp],
+    "vc2_gather_rows_grid": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp],
     "vc2_compress": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
                      _vp, _vp, _vp, _vp],
     "vc2_compress_ex": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
@@ -45,6 +46,8 @@ _SIGNATURES = {
                          _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
     "vc2_compress_ex4": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
                          _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp],
+    "vc2_compress_ex5": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
+                         _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i32, _vp, _vp],
     "vc2_wait_host_count": [_vp, _dbl],
     "vc2_pool_out_tokens": [_i64, _i64, _i32, _vp, _vp],
     "vc2_pool_stats": [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp],
@@ -204,7 +207,7 @@ def profile_enable(on: bool) -> None:
 
 def profile_collect() -> dict:
     """{kernel name: (total_ms, launches)} accumulated since profile_enable(True)."""
-    n = 16
+    n = 32
     names = (ctypes.c_char_p * n)()
     ms = (ctypes.c_double * n)()
     cnt = (ctypes.c_int64 * n)()

@@ -21,7 +21,7 @@ from torch.autograd.function import once_differentiable
 
 from ._ffi import DTYPE_CODE, check, lib, on_device, ptr, stream_ptr
 
-__all__ = ["wants_grad", "rows_grad", "cols_grad", "attach_rows", "attach_cols", "attach_pool"]
+__all__ = ["wants_grad", "rows_grad", "cols_grad", "attach_rows", "attach_rows_grid", "attach_cols", "attach_pool"]
 
 
 def wants_grad(*ts) -> bool:
@@ -146,6 +146,49 @@ def attach_rows(outs: Sequence[torch.Tensor], srcs: Sequence[torch.Tensor], idx:
                      tail_shape=tuple(tail.shape) if tail is not None else None, validate=bool(validate))
     # (detach: an output that is a view -- the kept rows sliced from a plan's buffer -- would refuse in-place use)
     return list(_GatherRows.apply(_Box([o.detach() for o in outs], spec), *srcs, tail))
+
+
+class _GatherRowsGrid(torch.autograd.Function):
+    """out = rows of the [F*h*(h+1), D] stream made of `flat` [F*h*h, D] and the [D] newline vector (the grid form of the
+    gather, vc2_gather_rows_grid), gathered by grid-space indices; `tail` rows may sit behind them.  The backward is
+    composed from what exists: the non-newline slots go through vc2_rows_grad (the newline slots become pad entries, -1,
+    which it skips), the newline slots' gradient rows are summed in fp32 and rounded once."""
+
+    @staticmethod
+    def forward(ctx, box, flat, newline, tail):
+        ctx.spec = box.spec
+        return box.outs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        idx, n, F, h, flat_shape, nl_shape, tail_shape, validate = ctx.spec
+        need_flat, need_nl, need_tail = ctx.needs_input_grad[1:4]
+        D = int(g.shape[-1])
+        g = g.reshape(-1, D)
+        g = g if g.is_contiguous() else g.contiguous()
+        gi = idx[:n]
+        w = h + 1
+        c = gi % w
+        is_nl = c == h
+        gflat = gnl = gtail = None
+        if need_flat:
+            src = torch.where(is_nl, torch.full_like(gi, -1), (gi // (h * w)) * (h * h) + ((gi % (h * w)) // w) * h + c)
+            gflat = rows_grad([g], [F * h * h], src.contiguous(), n, validate=validate)[0].view(flat_shape)
+        if need_nl:
+            gnl = g[:n][is_nl].float().sum(dim=0).to(g.dtype).reshape(nl_shape)
+        if need_tail and tail_shape is not None:
+            gtail = g[n: n + int(torch.Size(tail_shape[:-1]).numel())].reshape(tail_shape)
+        return None, gflat, gnl, gtail
+
+
+def attach_rows_grid(out: torch.Tensor, flat: torch.Tensor, newline: torch.Tensor, idx: torch.Tensor, n: int, F: int,
+                     h: int, tail: Optional[torch.Tensor] = None, validate: bool = False) -> torch.Tensor:
+    """The already gathered `out` (rows j < n <- slot idx[j] of the newline grid over `flat` and `newline`; tail rows
+    behind them) returned as the output of a differentiable gather with respect to `flat`, `newline` and `tail`."""
+    spec = (idx, int(n), int(F), int(h), tuple(flat.shape), tuple(newline.shape),
+            tuple(tail.shape) if tail is not None else None, bool(validate))
+    return _GatherRowsGrid.apply(_Box(out.detach(), spec), flat, newline, tail)
 
 
 class _GatherCols(torch.autograd.Function):

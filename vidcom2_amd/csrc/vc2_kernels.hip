@@ -4094,6 +4094,57 @@ __global__ __launch_bounds__(256) void k_gather_rows(GSArgs a) {   // (448 / 512
   if ((blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && t == 0 && threadIdx.x == 0) VC2_STAMP(909);
 }
 
+// The grid form of the row gather (vidcom2.py:93-96, :105-115; the reference's models/llava.py:118-127): idx[] holds
+// indices into the [F * h * (h + 1), D] stream add_token_per_grid would build -- every grid row of every frame followed by
+// the model's image_newline embedding -- and that stream is never built.  A row of it is either a row of the scored
+// tensor or the newline vector: g = f * h * (h + 1) + r * (h + 1) + c is source row f * h * h + r * h + c when c < h and
+// the [D] newline vector when c == h.  Same workgroup-per-row copy, device-side n, tail rows and status bit as
+// k_gather_rows, which stays as it is (its own kernel, its own argument block).
+struct GridGatherArgs {
+  const unsigned char* src;      // the scored tensor [F * h * h, D]
+  const unsigned char* newline;  // [D]
+  unsigned char* dst;            // [dst_rows, D]
+  int64_t grid_rows;             // F * h * (h + 1): the index space of idx[]
+  int64_t dst_rows;
+  int64_t row_bytes;
+  const int64_t* idx;            // [n] grid-space indices
+  const int64_t* n_dev;          // n on the device (null: n_max)
+  int64_t n_max;
+  const unsigned char* tail;     // rows appended behind the gathered ones (null: none)
+  int64_t tail_rows;
+  int* status;                   // null, or a device word: |= 2 when an index is outside [0, grid_rows)
+  int h;
+};
+__global__ __launch_bounds__(256) void k_gather_rows_grid(GridGatherArgs a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) VC2_STAMP(900);
+  const int64_t n = a.n_dev ? min(a.n_dev[0], a.n_max) : a.n_max;
+  const int64_t total = n + a.tail_rows;
+  const int64_t h = a.h, w = h + 1;
+  for (int64_t j = blockIdx.x; j < total; j += gridDim.x) {
+    if (j >= a.dst_rows) { if (a.status && threadIdx.x == 0) atomicOr(a.status, 2); continue; }
+    unsigned char* const d = a.dst + j * a.row_bytes;
+    if (j >= n) {                                                // the tail rows, behind the last gathered one
+      copy_row(a.tail + (j - n) * a.row_bytes, d, a.row_bytes);
+      continue;
+    }
+    const int64_t g = a.idx[j];
+    if (g < 0 || g >= a.grid_rows) { if (a.status && threadIdx.x == 0) atomicOr(a.status, 2); continue; }
+    int64_t f, r, c;
+    if (a.grid_rows <= int64_t(0xffffffffu)) {                   // (every real shape: 32-bit divisions)
+      const uint32_t g32 = uint32_t(g), w32 = uint32_t(w), fw = uint32_t(h) * w32;
+      const uint32_t f32 = g32 / fw, rem = g32 - f32 * fw, r32 = rem / w32;
+      f = f32; r = r32; c = rem - r32 * w32;
+    } else {
+      f = g / (h * w);
+      const int64_t rem = g - f * (h * w);
+      r = rem / w; c = rem - r * w;
+    }
+    if (c == h) copy_row(a.newline, d, a.row_bytes);
+    else copy_row(a.src + ((f * h + r) * h + c) * a.row_bytes, d, a.row_bytes);
+  }
+  if ((blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && threadIdx.x == 0) VC2_STAMP(909);
+}
+
 // Sequence positions a pruned prefill keeps (hooks, reference models/qwen2_5_vl.py:153-160): every position that is
 // not a video token, plus the video tokens whose ordinal is in `kept` (ascending).  keep_out = those positions in
 // order; vis_rows_out (optional) = for the positions flagged in visual_mask, the ordinals (among them) that are
@@ -4856,11 +4907,12 @@ int check_launch(const char* what) {
 // ---- optional per-kernel timing (bench.py's roofline leg): hipEvents around every launch --------
 enum KernelId { KID_STATS = 0, KID_STATS_REDUCE, KID_CHAN_SELECT, KID_NORM_COLSUM, KID_CENTRES, KID_DIST,
                 KID_EPILOGUE, KID_SCALES, KID_KS, KID_SELECT, KID_GATHER_ROWS, KID_OTHER, KID_CHAN_ORDER, KID_DIST_FIX,
-                KID_CENTRE_FIX, KID_VC_RECORDS, KID_COUNT };
+                KID_CENTRE_FIX, KID_VC_RECORDS, KID_GATHER_ROWS_GRID, KID_COUNT };
 const char* const kKernelNames[KID_COUNT] = {"k_chan_stats", "k_stats_reduce", "k_chan_select", "k_norm_colsum",
                                              "k_centres", "k_dist", "k_token_epilogue", "k_scales", "k_ks(unused)",
                                              "k_select", "k_gather_rows", "k_norm_fix", "k_chan_order",
-                                             "k_dist_fix", "k_centre_fix", "k_vc_records"};
+                                             "k_dist_fix", "k_centre_fix", "k_vc_records",
+                                             "k_gather_rows_grid"};
 struct ProfRec { int id; hipEvent_t a, b; };
 bool g_prof = false;                // (bench-only; the record list is mutex-protected)
 std::mutex g_prof_mu;
@@ -5350,6 +5402,23 @@ int launch_gather_rows(const void* src, int64_t src_rows, int64_t D, int ES, con
   a.row_bytes = D * ES; a.idx = idx; a.n_dev = K_dev; a.n_max = cap;
   a.tail = static_cast<const unsigned char*>(tail); a.tail_rows = tail ? tail_rows : 0;
   return launch_gather(a, 1, st);
+}
+// the grid form: kept rows of the scored tensor `src` [F * h * h, D] and newline rows from the [D] vector, idx[] in the
+// index space of the [F * h * (h + 1), D] stream (k_gather_rows_grid)
+int launch_gather_rows_grid(const void* src, int64_t F, int64_t h, int64_t D, int ES, const int64_t* idx,
+                            const int64_t* K_dev, int64_t cap, const void* newline, void* dst, hipStream_t st,
+                            const void* tail = nullptr, int64_t tail_rows = 0) {
+  GridGatherArgs a{};
+  a.src = static_cast<const unsigned char*>(src); a.newline = static_cast<const unsigned char*>(newline);
+  a.dst = static_cast<unsigned char*>(dst);
+  a.tail = static_cast<const unsigned char*>(tail); a.tail_rows = tail ? tail_rows : 0;
+  a.grid_rows = F * h * (h + 1); a.dst_rows = cap + a.tail_rows; a.row_bytes = D * ES;
+  a.idx = idx; a.n_dev = K_dev; a.n_max = cap; a.h = int(h);
+  const int64_t rows = a.n_max + a.tail_rows;
+  if (rows <= 0) return VC2_OK;
+  ProfScope ps_(KID_GATHER_ROWS_GRID, st);
+  hipLaunchKernelGGL(k_gather_rows_grid, dim3(unsigned(std::min<int64_t>(rows, 16384))), dim3(256), 0, st, a);
+  return check_launch("gather_rows_grid");
 }
 
 #endif   // VC2_DEV_ONLY
@@ -6184,6 +6253,15 @@ int vc2_gather_rows(const void* src, int64_t src_rows, int64_t D, int dtype, con
                             static_cast<hipStream_t>(stream));
 }
 
+int vc2_gather_rows_grid(const void* src, int64_t F, int64_t h, int64_t D, int dtype, const int64_t* idx,
+                         const int64_t* n_dev, int64_t n_max, const void* newline, void* out, void* stream) {
+  if (!src || !idx || !newline || !out) return fail(VC2_ERR_ARG, "null pointer");
+  if (dtype < VC2_F32 || dtype > VC2_F16 || F <= 0 || h <= 0 || h > 32768 || D <= 0 || n_max < 0)
+    return fail(VC2_ERR_ARG, "bad gather_rows_grid arguments");
+  return launch_gather_rows_grid(src, F, h, D, dtype == VC2_F32 ? 4 : 2, idx, n_dev, n_max, newline, out,
+                                 static_cast<hipStream_t>(stream));
+}
+
 int vc2_compress(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale, int map_mode,
                  int64_t grid_h, const void* gather_src, int64_t gather_rows, void* ws, size_t ws_bytes,
                  void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
@@ -6235,7 +6313,19 @@ int vc2_compress_ex4(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
                      void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
                      const void* tail, int64_t tail_rows, int flags, int64_t* K_host, const vc2_pass_params* params,
                      int score_dtype, void* stream) {
+  return vc2_compress_ex5(x, F, N, D, dtype, base_scale, map_mode, grid_h, gather_src, gather_rows, ws, ws_bytes, out_rows,
+                          idx_out, cap, ks, K_out, v_T, f_T, tail, tail_rows, flags, K_host, params, score_dtype, nullptr,
+                          stream);
+}
+
+int vc2_compress_ex5(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale, int map_mode,
+                     int64_t grid_h, const void* gather_src, int64_t gather_rows, void* ws, size_t ws_bytes,
+                     void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
+                     const void* tail, int64_t tail_rows, int flags, int64_t* K_host, const vc2_pass_params* params,
+                     int score_dtype, const void* newline, void* stream) {
   if (!x || !idx_out || !ks || !K_out) return fail(VC2_ERR_ARG, "null pointer");
+  if (newline && map_mode != VC2_MAP_GRID_VID)
+    return fail(VC2_ERR_ARG, "a newline vector needs the grid_vid mapping (map_mode %d)", map_mode);
   // score_dtype == dtype: the pass of vc2_compress_ex3, the same launches.  VC2_F32 over 16-bit rows: the library's storage /
   // arithmetic pair (vc2_device.h) -- 16-bit loads, the arithmetic (and the launches) of the fp32-input pass.
   if (dtype < VC2_F32 || dtype > VC2_F16) return fail(VC2_ERR_ARG, "unknown dtype code %d", dtype);
@@ -6344,7 +6434,9 @@ int vc2_compress_ex4(const void* x, int64_t F, int64_t N, int64_t D, int dtype, 
                                  reinterpret_cast<long long*>(K_host), wsp<int>(ws, p.o_ticket) + kTkSelArrive}, st);
   }
   if (rc) return rc;
-  if (out_rows && gather_src)
+  if (out_rows && newline)       // the grid form: kept rows straight from x, newline rows from the vector; gather_src unused
+    rc = launch_gather_rows_grid(x, F, grid_h, D, p.ES, idx_out, K_out, cap, newline, out_rows, st, tail, tail_rows);
+  else if (out_rows && gather_src)
     rc = launch_gather_rows(gather_src, gather_rows, D, p.ES, idx_out, K_out, cap, out_rows, st, tail, tail_rows);
   return rc;
 }

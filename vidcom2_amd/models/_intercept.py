@@ -123,6 +123,16 @@ def params_kwargs() -> dict:
     return kw
 
 
+def grid_newline_enabled() -> bool:
+    """`VC2_GRID_NEWLINE` env knob, `on` by default, read at call time: LLaVA-Video's grid hook gathers the kept rows from
+    the pooled features and the model's `image_newline` vector instead of building the newline stream with the model's
+    `add_token_per_grid` (same result, bit for bit).  `off`: the model's own method builds the stream, as before."""
+    raw = os.getenv("VC2_GRID_NEWLINE", "on")
+    if raw not in ("on", "off"):
+        raise ValueError(f"VC2_GRID_NEWLINE={raw!r}: expected 'on' or 'off'")
+    return raw == "on"
+
+
 def compressor_enabled() -> bool:
     """`COMPRESSOR=vidcom2` env knob (models/qwen2_5_vl.py:121)."""
     return os.getenv("COMPRESSOR") == "vidcom2"

@@ -27,7 +27,7 @@ import torch
 
 from ..autograd import attach_pool, wants_grad
 from ..vidcom2 import vidcom2_compression
-from ._intercept import original_method, params_kwargs, retention_ratio, shadow
+from ._intercept import grid_newline_enabled, original_method, params_kwargs, retention_ratio, shadow
 
 __all__ = ["cus_prepare_inputs_labels_for_multimodal"]
 
@@ -127,6 +127,17 @@ def _fused_pool(model, pool_inner, image_feature, args, kwargs):
     return out, ws
 
 
+def _grid_newline_applies(image_feature, newline) -> bool:
+    """Does the grid branch take the route without the newline stream?  Pooled features [F, 169, D] on a ROCm device, the
+    model's image_newline a [D] tensor of their dtype on their device, and the VC2_GRID_NEWLINE knob not `off`."""
+    from ..vidcom2 import MODEL_SPECS
+    return (torch.is_tensor(image_feature) and image_feature.is_cuda and image_feature.dim() == 3
+            and image_feature.shape[1] == MODEL_SPECS["llava_vid"]["tpf"] and torch.is_tensor(newline)
+            and newline.dim() == 1 and newline.shape[0] == image_feature.shape[-1]
+            and newline.dtype == image_feature.dtype and newline.device == image_feature.device
+            and grid_newline_enabled())
+
+
 def cus_prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values,
                                              labels, images, modalities=["image"], image_sizes=None):
     original = original_method(self, "prepare_inputs_labels_for_multimodal",
@@ -142,8 +153,23 @@ def cus_prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, atte
             grid_inner = self.add_token_per_grid
             faster = bool(getattr(cfg, "add_faster_video", False))
             calls = [0]
+            inner_g = getattr(self, "model", None)
+            newline_g = getattr(inner_g, "image_newline", None) if inner_g is not None else None
 
             def add_token_per_grid(image_feature):
+                # LLaVA-Video's usual case: the [F*13*14, D] stream exists only to be indexed, so it is not built -- the
+                # gather reads the kept rows from the pooled features and writes image_newline into the newline slots
+                # (same bits; VC2_GRID_NEWLINE=off keeps the model's own add_token_per_grid)
+                # (an autograd graph being recorded: the model's own method builds the stream, so that a training run keeps
+                #  torch's own backward of it, bit for bit)
+                if not faster and _grid_newline_applies(image_feature, newline_g) \
+                        and not wants_grad(image_feature, newline_g):
+                    from ..vidcom2 import MODEL_SPECS, compress
+                    spec = MODEL_SPECS["llava_vid"]
+                    nl = newline_g.detach()
+                    return compress(image_feature.reshape(-1, image_feature.shape[-1]), spec["tpf"], retention_ratio(),
+                                    "grid_vid", spec["grid"], newline=nl,
+                                    stats_ws=getattr(image_feature, "_vc2_stats_ws", None), **params_kwargs()).rows
                 out = grid_inner(image_feature)
                 calls[0] += 1
                 if faster and calls[0] % 2 == 0:

@@ -185,6 +185,20 @@ def _prep(x: torch.Tensor, what: str) -> torch.Tensor:
     return x if x.data_ptr() % 16 == 0 else x.clone()
 
 
+def _prep_newline(newline, D: int, dtype, device) -> torch.Tensor:
+    """The grid mapping's newline vector (the model's `image_newline`) as the [D] tensor the gather launch reads: [D] or
+    [1, D], the input's dtype, on its device.  A non-contiguous one is copied; a misaligned one (a view at an odd element
+    offset) is NOT: the gather takes its scalar copy path for those rows."""
+    device = torch.device(device)
+    if not isinstance(newline, torch.Tensor) or tuple(newline.shape) not in ((D,), (1, D)) or newline.dtype != dtype \
+            or newline.device.type != device.type or (device.index is not None and newline.device.index != device.index):
+        got = f"{tuple(newline.shape)} {newline.dtype} on {newline.device}" if isinstance(newline, torch.Tensor) \
+            else type(newline).__name__
+        raise RuntimeError(f"newline must be a [{D}] or [1, {D}] {dtype} tensor on {device}, got {got}")
+    newline = newline.detach().reshape(D)
+    return newline if newline.is_contiguous() else newline.contiguous()
+
+
 @dataclass
 class CompressionResult:
     """Everything one pass produces (device tensors; ``K`` / ``ks`` are synced to host lazily)."""
@@ -335,11 +349,21 @@ class CompressPlan:
 
     def enqueue(self, flat: torch.Tensor, gather_src: Optional[torch.Tensor] = None,
                 tail: Optional[torch.Tensor] = None, have_stats: bool = False, mirror: bool = False,
-                stream: Optional["torch.cuda.Stream"] = None, out: Optional[OutputSet] = None) -> None:
+                stream: Optional["torch.cuda.Stream"] = None, out: Optional[OutputSet] = None,
+                newline: Optional[torch.Tensor] = None) -> None:
         """have_stats: `self.ws` already holds flat's sweep-1 partials (fused.pool_stats wrote them on this
         stream), so the pass starts at the variance reduction.  mirror: the count is also written to pinned host
         memory (finish(early=True)).  out: the output set to write (one this plan's `_alloc_outputs` could have made;
-        the caller reads it) instead of the plan's own."""
+        the caller reads it) instead of the plan's own.  newline (grid_vid plans, instead of gather_src): the model's
+        [D] newline embedding -- the gather reads the kept rows from `flat` and the newline rows from the vector, the
+        [F*h*(h+1), D] stream is never built (vidcom2.py:93-96, :105-115).  The pointer belongs to this call alone:
+        nothing of it stays in the plan."""
+        if newline is not None:
+            if self.map_mode != MAP_GRID_VID:
+                raise ValueError("newline is the grid_vid mapper's newline vector; this plan maps linearly")
+            if gather_src is not None:
+                raise ValueError("give either gather_src (img_feat) or newline, not both")
+            newline = _prep_newline(newline, self.D, self.dtype, self.device)
         src = flat if gather_src is None else gather_src
         o = self.out if out is None else out
         if have_stats:
@@ -366,14 +390,14 @@ class CompressPlan:
             khost = kh.addr
         self._armed = st if mirror else None
         with on_device(self.device):
-            rc = lib().vc2_compress_ex4(ptr(flat), self.F, self.N, self.D, DTYPE_CODE[self.dtype], self.base_scale,
+            rc = lib().vc2_compress_ex5(ptr(flat), self.F, self.N, self.D, DTYPE_CODE[self.dtype], self.base_scale,
                                         self.map_mode, self.grid_h, ptr(src if o.rows is not None else None),
                                         src.shape[0], ptr(self.ws), self.ws.numel(), ptr(o.rows), ptr(o.idx),
                                         self.cap, ptr(o.ks), ptr(o.kout), ptr(o.v), ptr(o.f),
                                         ptr(tail if self.tail_rows else None), self.tail_rows,
                                         1 if have_stats else 0, khost,
                                         None if self._cparams is None else ctypes.addressof(self._cparams),
-                                        DTYPE_CODE[self.arith_dtype], ctypes.c_void_p(st.cuda_stream))
+                                        DTYPE_CODE[self.arith_dtype], ptr(newline), ctypes.c_void_p(st.cuda_stream))
         if rc != 0 and mirror:                           # (nothing was launched: the mirror block is not in flight)
             self._khost.in_flight = False
             self._armed = None
@@ -590,8 +614,12 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
              grid_h: int = 0, img_feat: Optional[torch.Tensor] = None, want_scores: bool = False,
              gather: bool = True, tail: Optional[torch.Tensor] = None,
              stats_ws: Optional[torch.Tensor] = None, score_dtype: Optional[torch.dtype] = None,
-             params: Optional[PassParams] = None) -> CompressionResult:
+             newline: Optional[torch.Tensor] = None, params: Optional[PassParams] = None) -> CompressionResult:
     """One whole pass: feature tensor resident in HBM -> kept rows + indices + budgets.
+    newline (mapper "grid_vid", INSTEAD of img_feat): the model's `image_newline` embedding, [D] or [1, D] in the input's
+    dtype.  `rows` is then bit for bit `img_feat[global_idx]` for the img_feat LLaVA-Video's add_token_per_grid builds from
+    `flattened_feat` and that vector -- without building it: the gather reads the kept rows from `flattened_feat` and
+    writes the vector into the newline slots (vidcom2.py:93-96, :105-115).  Indices, K and budgets are unchanged.
     score_dtype: the dtype the pass scores in.  None or the input's dtype: the reference's behaviour (every op rounds to the
     input dtype).  torch.float32 over a bf16 / fp16 tensor: the reference applied to `flattened_feat.float()` -- the kept set
     a user gets today from `compress(x.float(), ...)` -- from the 16-bit tensor itself: no fp32 copy, half the bytes, rows
@@ -602,8 +630,18 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     `rows` is then [K + m, D].  stats_ws: the workspace `fused.pool_stats` returned together with THIS tensor --
     the pass then skips its first sweep.
     Autograd: `rows` is differentiable (vidcom2_amd/autograd.py) with respect to the gathered-from tensor
-    (`flattened_feat`, or `img_feat` for grid_vid -- flattened_feat then gets none, as in the reference) and `tail`;
-    indices, budgets and scores are not."""
+    (`flattened_feat`, or `img_feat` for grid_vid -- flattened_feat then gets none, as in the reference; with `newline`
+    both `flattened_feat` and `newline`, as through the stream built from them) and `tail`; indices, budgets and scores are
+    not."""
+    if isinstance(newline, PassParams) and params is None:
+        # (`newline` took the twelfth position, which was `params`' before it existed: a PassParams handed over
+        #  positionally still means what it meant)
+        params, newline = newline, None
+    if newline is not None:               # (argument errors first: nothing has touched the device yet)
+        if mapper != "grid_vid":
+            raise ValueError(f"newline is the grid_vid mapper's newline vector; got mapper={mapper!r}")
+        if img_feat is not None:
+            raise ValueError("give either img_feat or newline for grid mapping, not both")
     params = _norm_params(params)
     x = _prep(flattened_feat, "flattened_feat")
     score_dtype = _norm_score_dtype(score_dtype, x.dtype)
@@ -617,7 +655,10 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
         C = int(D * 0.5) if params is None else params.channels(D)
         raise RuntimeError(f"shape '[-1, {tpf}, {C}]' is invalid for input of size {R * C}")
     src = None
-    if mapper == "grid_vid":
+    nl = None
+    if mapper == "grid_vid" and newline is not None:
+        nl = _prep_newline(newline, D, x.dtype, x.device)
+    elif mapper == "grid_vid":
         if img_feat is None:
             raise ValueError("img_feat required for grid mapping")
         src = _prep(img_feat, "img_feat")
@@ -643,11 +684,16 @@ def compress(flattened_feat: torch.Tensor, tpf: int, base_scale: float = 0.25, m
     else:
         plan = _cached_plan(R // tpf, tpf, D, x.dtype, x.device, base_scale, mapper, grid_h, want_scores, gather, ntail,
                             fresh_outputs=True, params=params, score_dtype=score_dtype)
-    plan.enqueue(x, src, tail, have_stats=stats_ws is not None, mirror=_EARLY_COUNT)
+    plan.enqueue(x, src, tail, have_stats=stats_ws is not None, mirror=_EARLY_COUNT, newline=nl)
     if stats_ws is None and _PREALLOC and _PLAN_CACHE_MAX > 0 and plan.output_bytes() <= _SPARE_MAX_BYTES:
         plan.prepare_spare()              # (the GPU is busy for the next ~190 us: the next call's outputs cost nothing here)
     res = plan.finish()
     _check_budgets(res.ks, tpf, plan.arith_dtype)        # (RN_T(scale * N) rounds in the dtype the pass scores in)
+    if nl is not None:
+        if gather and _ag.wants_grad(flattened_feat, newline, tail_user):
+            res.rows = _ag.attach_rows_grid(res.rows, flattened_feat, newline, res.global_idx, res.K, R // tpf, int(grid_h),
+                                            tail=tail_user)
+        return res
     gsrc = img_feat if mapper == "grid_vid" else flattened_feat
     if gather and _ag.wants_grad(gsrc, tail_user):
         res.rows = _ag.attach_rows([res.rows], [gsrc], res.global_idx, res.K, tail=tail_user)[0]
@@ -1004,15 +1050,39 @@ def _gather_rows(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _gather_rows_grid(flat: torch.Tensor, idx: torch.Tensor, newline: torch.Tensor, F: int, h: int) -> torch.Tensor:
+    """rows idx[] (grid index space) of the [F*h*(h+1), D] stream made of `flat` [F*h*h, D] and the newline vector."""
+    flat_user = flat
+    flat = _prep(flat, "features")
+    if flat.dim() != 2 or flat.shape[0] != F * h * h:
+        raise RuntimeError(f"features must be [{F} * {h} * {h}, dim] for {F} frames on a {h} x {h} grid, got "
+                           f"{tuple(flat.shape)}")
+    D = flat.shape[1]
+    nl = _prep_newline(newline, D, flat.dtype, flat.device)
+    K = idx.numel()
+    out = torch.empty((K, D), dtype=flat.dtype, device=flat.device)
+    if K:
+        check(lib().vc2_gather_rows_grid(ptr(flat), F, h, D, DTYPE_CODE[flat.dtype], ptr(idx), None, K, ptr(nl), ptr(out),
+                                         stream_ptr(flat.device)), "vc2_gather_rows_grid")
+    if _ag.wants_grad(flat_user, newline):
+        out = _ag.attach_rows_grid(out, flat_user, newline, idx, K, F, h, validate=True)
+    return out
+
+
 @_guarded
 def map_features(indices: List[torch.Tensor], flat: torch.Tensor, img: Optional[torch.Tensor],
-                 spec: Dict[str, Any]) -> torch.Tensor:
-    """Reference: vidcom2.py:80-97."""
+                 spec: Dict[str, Any], *, newline: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Reference: vidcom2.py:80-97.  newline (a grid_vid spec, with img None): the model's [D] newline embedding -- the rows
+    of the stream add_token_per_grid would build from `flat` and it, gathered without building it (vc2_gather_rows_grid)."""
     if spec["mapper"] == "linear":
         stride = flat.shape[0] // len(indices)                     # vidcom2.py:89
         return _gather_rows(flat, _map_linear_offset(indices, stride))
     elif spec["mapper"] == "grid_vid":
+        if img is None and newline is not None:
+            return _gather_rows_grid(flat, _map_grid_vid(indices, spec["grid"]), newline, len(indices), int(spec["grid"]))
         if img is None:
             raise ValueError("img_feat required for grid mapping")
+        if newline is not None:
+            raise ValueError("give either img or newline for grid mapping, not both")
         return _gather_rows(img, _map_grid_vid(indices, spec["grid"]))
     return flat
