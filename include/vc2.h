@@ -170,6 +170,20 @@ int vc2_gather_rows(const void* src, int64_t src_rows, int64_t D, int dtype, con
 int vc2_gather_rows_grid(const void* src, int64_t F, int64_t h, int64_t D, int dtype, const int64_t* idx,
                          const int64_t* n_dev, int64_t n_max, const void* newline, void* out, void* stream);
 
+/* vidcom2.py:89-91  flat[global_idx] for a video that lies in n_chunks allocations (a vision tower that encodes a few
+ * dozen frames at a time): idx[] holds rows of the virtual concatenation of the chunks, chunk c holding chunk_rows[c]
+ * rows of D elements, and dst[j,:] = chunk_c[idx[j] - start_c,:] for j < min(n_dev[0], n_max) (n_dev NULL: n_max), c the
+ * chunk with start_c <= idx[j] < start_c + chunk_rows[c], start_c = chunk_rows[0] + ... + chunk_rows[c-1].  chunks and
+ * chunk_rows are HOST arrays (chunks[c]: a device pointer); the table reaches the kernel by value: no copy, no
+ * synchronisation.  An index outside [0, sum chunk_rows) or a destination row j >= dst_rows is skipped and reported:
+ * *status |= 2 (status: a device word the caller zeroed, or NULL).  Rows of any alignment (16 bytes per lane when the row
+ * bytes and both addresses allow it).  n_chunks outside 1..VC2_RAGGED_MAX_WORLD: VC2_ERR_UNSUPPORTED; a null chunks /
+ * chunk_rows / idx / dst or chunk pointer, or a chunk_rows entry < 1: VC2_ERR_ARG; nothing is enqueued. */
+int vc2_gather_rows_chunks(const void* const* chunks /* host [n_chunks] device pointers */,
+                           const int64_t* chunk_rows /* host [n_chunks] */, int n_chunks, int64_t D, int dtype,
+                           const int64_t* idx, const int64_t* n_dev, int64_t n_max, void* dst, int64_t dst_rows,
+                           int32_t* status, void* stream);
+
 /* ---- one-shot hot path -------------------------------------------------------------- */
 
 /* vidcom2.py:15-36  vidcom2_compression for the "linear" mapper (llava_ov / qwen*), and for
@@ -596,6 +610,32 @@ int vc2_select_sharded_o(const float* total_f32, const float* s_all_f32, int64_t
                          int64_t F_local, int64_t N, int64_t D, double base_scale, int dtype, void* ws,
                          size_t ws_bytes, int64_t* ks, int64_t* idx_out, int64_t cap, int64_t* K_out,
                          const void* gather_src, void* out_rows, void* stream, const vc2_shard_opts* opts);
+
+/* ---- one video held as frame chunks on ONE device (vidcom2_amd/chunked.py) -------------------------------------------
+ * Every chunk is a logical rank of the frame-sharded pass above, its stage calls writing their partials into slots of
+ * whole-video buffers.  vc2_select_chunks is step 3 for the whole video in one call -- vidcom2.py:70-78,89-91:
+ *   budgets over all F_total frames, once; the per-frame selection of every frame from total_f32[F_total * N] and
+ *   s_all_f32[F_total] (vc2_select_sharded's launches with f0 = 0, F_local = F_total); ks[F_total], idx_out (ascending
+ *   indices into the virtual concatenation of the chunks, at most `cap` = the unsharded pass's capacity for F_total
+ *   frames), K_out[3] as in vc2_select_sharded; then, when out_rows [cap, D] is given, the kept rows from the chunk
+ *   table as vc2_gather_rows_chunks gathers them (chunks / chunk_rows / n_chunks / status as there; the chunks must hold
+ *   F_total * N rows: VC2_ERR_ARG otherwise).  out_rows NULL: no gather, the table is not looked at.
+ *   sel_ws      device scratch of vc2_select_chunks_ws_bytes(F_total) bytes (frame offsets, budgets)
+ *   stage_ws    the workspace of ONE of the chunks' stage calls and that chunk's frame count stage_frames: K_out[2], the
+ *               number of video-centre values left at the exactly rounded mean, is read from it (every chunk's phase 2
+ *               holds the same count)
+ * The `_o` form takes the pass's vc2_shard_opts (softmax temperature, score_dtype), NULL being the plain symbol. */
+int vc2_select_chunks_ws_bytes(int64_t F_total, size_t* out_bytes);
+int vc2_select_chunks(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t N, int64_t D,
+                      double base_scale, int dtype, void* sel_ws, size_t sel_ws_bytes, const void* stage_ws,
+                      size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
+                      int64_t* K_out, const void* const* chunks /* host */, const int64_t* chunk_rows /* host */,
+                      int n_chunks, void* out_rows, int32_t* status, void* stream);
+int vc2_select_chunks_o(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t N, int64_t D,
+                        double base_scale, int dtype, void* sel_ws, size_t sel_ws_bytes, const void* stage_ws,
+                        size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
+                        int64_t* K_out, const void* const* chunks /* host */, const int64_t* chunk_rows /* host */,
+                        int n_chunks, void* out_rows, int32_t* status, void* stream, const vc2_shard_opts* opts);
 
 /* _multi_scale_gaussian(x, center, alphas) as a standalone call -- vidcom2.py:59-62 (the fused pass
  * never materialises x; this entry serves callers of the helper itself).  x: T[F*N, C] as given,

@@ -19,6 +19,7 @@ from .vidcom2 import (  # noqa: F401
     CompressionResult,
     PassParams,
 )
+from .chunked import compress_chunks, ChunkedCompressor  # noqa: F401
 
 __all__ = [
     "vidcom2_compression",

@@ -36,6 +36,7 @@ _SIGNATURES = {
     "vc2_map_indices": [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp],
     "vc2_gather_rows": [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp],
     "vc2_gather_rows_grid": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp],
+    "vc2_gather_rows_chunks": [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
     "vc2_compress": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
                      _vp, _vp, _vp, _vp],
     "vc2_compress_ex": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
@@ -81,6 +82,9 @@ _SIGNATURES = {
                                         _i32, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "vc2_select_sharded": [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _dbl, _i32, _vp, _sz, _vp, _vp, _i64, _vp, _vp,
                            _vp, _vp],
+    "vc2_select_chunks_ws_bytes": [_i64, ctypes.POINTER(_sz)],
+    "vc2_select_chunks": [_vp, _vp, _i64, _i64, _i64, _dbl, _i32, _vp, _sz, _vp, _sz, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
+                          _i32, _vp, _vp, _vp],
     "vc2_multi_scale_gaussian": [_vp, _i64, _i64, _i64, _i32, _vp, _i64, ctypes.POINTER(ctypes.c_double), _i32, _vp, _vp],
     "vc2_kat_exp": [_vp, _i64, _i32, _vp, _vp],
     "vc2_kat_round": [_vp, _i64, _i32, _vp, _vp],
@@ -103,7 +107,7 @@ _RESTYPES = {"vc2_kept_capacity": _i64, "vc2_wait_host_count": _i64,  "vc2_last_
 for _name in ("vc2_chan_stats", "vc2_scores_phase1", "vc2_video_centre_blocks", "vc2_scores_phase2_blocks",
               "vc2_video_centre_blocks_round", "vc2_video_centre_finish_round", "vc2_video_centre_blocks_ragged",
               "vc2_video_centre_blocks_round_ragged", "vc2_video_centre_finish_round_ragged",
-              "vc2_scores_phase2_blocks_ragged", "vc2_select_sharded"):
+              "vc2_scores_phase2_blocks_ragged", "vc2_select_sharded", "vc2_select_chunks"):
     _SIGNATURES[_name + "_o"] = _SIGNATURES[_name] + [_vp]
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

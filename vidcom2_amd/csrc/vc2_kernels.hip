@@ -14,6 +14,7 @@
 //            k_select          softmax budgets, ks, per-frame bottom-k (libstdc++ ties) + map
 //                                                                              vidcom2.py:64-77,99-115
 //            k_gather_rows     kept rows (+ tail rows; several tensors)       vidcom2.py:91,96
+//            k_gather_rows_chunks  kept rows of a video held as several tensors vidcom2.py:91
 //   "torch order" mode: values whose exact result lies next to a T rounding boundary are replayed in torch's fp32
 //   accumulation order -- inside the sweeps' own workgroups (distances, centre means) or by k_norm_fix (norms)
 //   (DESIGN.md "Numerics contract").
@@ -4145,6 +4146,43 @@ __global__ __launch_bounds__(256) void k_gather_rows_grid(GridGatherArgs a) {
   if ((blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && threadIdx.x == 0) VC2_STAMP(909);
 }
 
+// The chunked form of the row gather (vidcom2.py:91 for a video that lies in several allocations, chunked.py): idx[] holds
+// rows of the virtual concatenation of n_chunks tensors [rows_c, D]; dst[j] = chunk_c[idx[j] - start_c] for the chunk c
+// with start_c <= idx[j] < start_{c+1}.  The chunk table -- the base pointers and the prefix sums of the row counts --
+// reaches the kernel by value, like the rank table of the ragged exchange-2b kernels (VC2_RAGGED_MAX_WORLD entries at
+// most): no device copy, no synchronisation.  The owner of a row is found once per row by a binary search that is
+// uniform for the workgroup.  Same workgroup-per-row copy, device-side n and status bit as k_gather_rows, which stays as
+// it is (its own kernel, its own argument block).
+constexpr int kChunkMax = VC2_RAGGED_MAX_WORLD;
+struct ChunkGatherArgs {
+  const unsigned char* src[kChunkMax];   // base of every chunk
+  int64_t start[kChunkMax + 1];          // start[c] = rows in front of chunk c; start[n_chunks] = rows of the video
+  unsigned char* dst;                    // [dst_rows, D]
+  int64_t dst_rows;
+  int64_t row_bytes;
+  const int64_t* idx;                    // [n] rows of the virtual concatenation
+  const int64_t* n_dev;                  // n on the device (null: n_max)
+  int64_t n_max;
+  int* status;                           // null, or a device word: |= 2 for an index outside the video or a row past dst
+  int n_chunks;
+};
+__global__ __launch_bounds__(256) void k_gather_rows_chunks(ChunkGatherArgs a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) VC2_STAMP(900);
+  const int64_t n = a.n_dev ? min(a.n_dev[0], a.n_max) : a.n_max;
+  const int64_t rows = a.start[a.n_chunks];
+  for (int64_t j = blockIdx.x; j < n; j += gridDim.x) {
+    const int64_t r = a.idx[j];
+    if (r < 0 || r >= rows || j >= a.dst_rows) { if (a.status && threadIdx.x == 0) atomicOr(a.status, 2); continue; }
+    int lo = 0, hi = a.n_chunks;                                 // start[lo] <= r < start[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (r >= a.start[mid]) lo = mid; else hi = mid;
+    }
+    copy_row(a.src[lo] + (r - a.start[lo]) * a.row_bytes, a.dst + j * a.row_bytes, a.row_bytes);
+  }
+  if ((blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && threadIdx.x == 0) VC2_STAMP(909);
+}
+
 // Sequence positions a pruned prefill keeps (hooks, reference models/qwen2_5_vl.py:153-160): every position that is
 // not a video token, plus the video tokens whose ordinal is in `kept` (ascending).  keep_out = those positions in
 // order; vis_rows_out (optional) = for the positions flagged in visual_mask, the ordinals (among them) that are
@@ -4907,12 +4945,12 @@ int check_launch(const char* what) {
 // ---- optional per-kernel timing (bench.py's roofline leg): hipEvents around every launch --------
 enum KernelId { KID_STATS = 0, KID_STATS_REDUCE, KID_CHAN_SELECT, KID_NORM_COLSUM, KID_CENTRES, KID_DIST,
                 KID_EPILOGUE, KID_SCALES, KID_KS, KID_SELECT, KID_GATHER_ROWS, KID_OTHER, KID_CHAN_ORDER, KID_DIST_FIX,
-                KID_CENTRE_FIX, KID_VC_RECORDS, KID_GATHER_ROWS_GRID, KID_COUNT };
+                KID_CENTRE_FIX, KID_VC_RECORDS, KID_GATHER_ROWS_GRID, KID_GATHER_ROWS_CHUNKS, KID_COUNT };
 const char* const kKernelNames[KID_COUNT] = {"k_chan_stats", "k_stats_reduce", "k_chan_select", "k_norm_colsum",
                                              "k_centres", "k_dist", "k_token_epilogue", "k_scales", "k_ks(unused)",
                                              "k_select", "k_gather_rows", "k_norm_fix", "k_chan_order",
                                              "k_dist_fix", "k_centre_fix", "k_vc_records",
-                                             "k_gather_rows_grid"};
+                                             "k_gather_rows_grid", "k_gather_rows_chunks"};
 struct ProfRec { int id; hipEvent_t a, b; };
 bool g_prof = false;                // (bench-only; the record list is mutex-protected)
 std::mutex g_prof_mu;
@@ -5419,6 +5457,32 @@ int launch_gather_rows_grid(const void* src, int64_t F, int64_t h, int64_t D, in
   ProfScope ps_(KID_GATHER_ROWS_GRID, st);
   hipLaunchKernelGGL(k_gather_rows_grid, dim3(unsigned(std::min<int64_t>(rows, 16384))), dim3(256), 0, st, a);
   return check_launch("gather_rows_grid");
+}
+
+// the chunked form: kept rows of a video that lies in n_chunks allocations (k_gather_rows_chunks).  The table is checked
+// here: nothing is enqueued on a bad one
+int launch_gather_rows_chunks(const void* const* chunks, const int64_t* chunk_rows, int n_chunks, int64_t D, int ES,
+                              const int64_t* idx, const int64_t* n_dev, int64_t n_max, void* dst, int64_t dst_rows,
+                              int* status, hipStream_t st) {
+  if (n_chunks < 1 || n_chunks > kChunkMax)
+    return fail(VC2_ERR_UNSUPPORTED, "%d chunks: between 1 and %d are supported", n_chunks, kChunkMax);
+  if (!chunks || !chunk_rows || !idx || !dst) return fail(VC2_ERR_ARG, "null pointer");
+  if (D <= 0 || n_max < 0 || dst_rows < 0) return fail(VC2_ERR_ARG, "bad gather_rows_chunks arguments");
+  ChunkGatherArgs a{};
+  a.start[0] = 0;
+  for (int c = 0; c < n_chunks; ++c) {
+    if (!chunks[c]) return fail(VC2_ERR_ARG, "chunk %d: null pointer", c);
+    if (chunk_rows[c] < 1) return fail(VC2_ERR_ARG, "chunk %d holds %lld rows", c, (long long)chunk_rows[c]);
+    a.src[c] = static_cast<const unsigned char*>(chunks[c]);
+    a.start[c + 1] = a.start[c] + chunk_rows[c];
+  }
+  for (int c = n_chunks; c < kChunkMax; ++c) a.start[c + 1] = a.start[n_chunks];
+  a.dst = static_cast<unsigned char*>(dst); a.dst_rows = dst_rows; a.row_bytes = D * ES;
+  a.idx = idx; a.n_dev = n_dev; a.n_max = n_max; a.status = status; a.n_chunks = n_chunks;
+  if (n_max == 0) return VC2_OK;
+  ProfScope ps_(KID_GATHER_ROWS_CHUNKS, st);
+  hipLaunchKernelGGL(k_gather_rows_chunks, dim3(unsigned(std::min<int64_t>(n_max, 16384))), dim3(256), 0, st, a);
+  return check_launch("gather_rows_chunks");
 }
 
 #endif   // VC2_DEV_ONLY
@@ -6262,6 +6326,16 @@ int vc2_gather_rows_grid(const void* src, int64_t F, int64_t h, int64_t D, int d
                                  static_cast<hipStream_t>(stream));
 }
 
+int vc2_gather_rows_chunks(const void* const* chunks, const int64_t* chunk_rows, int n_chunks, int64_t D, int dtype,
+                           const int64_t* idx, const int64_t* n_dev, int64_t n_max, void* dst, int64_t dst_rows,
+                           int32_t* status, void* stream) {
+  if (n_chunks < 1 || n_chunks > kChunkMax)
+    return fail(VC2_ERR_UNSUPPORTED, "%d chunks: between 1 and %d are supported", n_chunks, kChunkMax);
+  if (dtype < VC2_F32 || dtype > VC2_F16) return fail(VC2_ERR_ARG, "unknown dtype code %d", dtype);
+  return launch_gather_rows_chunks(chunks, chunk_rows, n_chunks, D, dtype == VC2_F32 ? 4 : 2, idx, n_dev, n_max, dst,
+                                   dst_rows, status, static_cast<hipStream_t>(stream));
+}
+
 int vc2_compress(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale, int map_mode,
                  int64_t grid_h, const void* gather_src, int64_t gather_rows, void* ws, size_t ws_bytes,
                  void* out_rows, int64_t* idx_out, int64_t cap, int64_t* ks, int64_t* K_out, void* v_T, void* f_T,
@@ -6484,6 +6558,85 @@ int vc2_select_sharded(const float* total_f32, const float* s_all_f32, int64_t F
                        size_t ws_bytes, int64_t* ks, int64_t* idx_out, int64_t cap, int64_t* K_out,
                        const void* gather_src, void* out_rows, void* stream) {
   return vc2_select_sharded_o(total_f32, s_all_f32, F_total, f0, F_local, N, D, base_scale, dtype, ws, ws_bytes, ks, idx_out, cap, K_out, gather_src, out_rows, stream, nullptr);
+}
+
+// the selection scratch of vc2_select_chunks: [offsets int64[F_total + 1] | softmax scratch float[F_total] | budgets
+// float[F_total]]
+struct SelChunksWs { size_t o_offs, o_zbuf, o_scales, total_bytes; };
+static SelChunksWs sel_chunks_ws(int64_t F_total) {
+  SelChunksWs w;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t r = o; o += align_up(bytes); return r; };
+  w.o_offs = take(size_t(F_total + 1) * 8);
+  w.o_zbuf = take(size_t(F_total) * 4);
+  w.o_scales = take(size_t(F_total) * 4);
+  w.total_bytes = o;
+  return w;
+}
+int vc2_select_chunks_ws_bytes(int64_t F_total, size_t* out_bytes) {
+  if (!out_bytes) return fail(VC2_ERR_ARG, "out_bytes is null");
+  if (F_total <= 0 || F_total > kMaxFramesTotal) return fail(VC2_ERR_ARG, "bad frame count %lld", (long long)F_total);
+  *out_bytes = sel_chunks_ws(F_total).total_bytes;
+  return VC2_OK;
+}
+
+int vc2_select_chunks_o(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t N, int64_t D,
+                        double base_scale, int dtype, void* sel_ws, size_t sel_ws_bytes, const void* stage_ws,
+                        size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
+                        int64_t* K_out, const void* const* chunks, const int64_t* chunk_rows, int n_chunks, void* out_rows,
+                        int32_t* status, void* stream, const vc2_shard_opts* opts) {
+  if (!total_f32 || !s_all_f32 || !ks || !idx_out || !K_out || !sel_ws || !stage_ws) return fail(VC2_ERR_ARG, "null pointer");
+  if (F_total <= 0 || F_total > kMaxFramesTotal || stage_frames <= 0 || stage_frames > F_total || cap < 0)
+    return fail(VC2_ERR_ARG, "bad frame counts (%lld of %lld) or capacity", (long long)stage_frames, (long long)F_total);
+  if (N <= 0) return fail(VC2_ERR_ARG, "N must be positive");
+  if (N > 8192) return fail(VC2_ERR_UNSUPPORTED, "N=%lld > 8192 tokens per frame", (long long)N);
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, 0, &so); if (rco) return rco; }
+  Plan p;                                   // the stage's workspace: only its count of fragile centre columns is read
+  int rc = make_plan(stage_frames, N, D, so.pdt, &p, F_total, 0, opts != nullptr);
+  if (rc) return rc;
+  if ((rc = need_ws(p, const_cast<void*>(stage_ws), stage_ws_bytes))) return rc;
+  const SelChunksWs w = sel_chunks_ws(F_total);
+  if (sel_ws_bytes < w.total_bytes)
+    return fail(VC2_ERR_WORKSPACE, "selection scratch too small: %zu < %zu bytes", sel_ws_bytes, w.total_bytes);
+  if (out_rows) {                           // the chunk table must be this video's (checked before anything is enqueued)
+    if (n_chunks < 1 || n_chunks > kChunkMax)
+      return fail(VC2_ERR_UNSUPPORTED, "%d chunks: between 1 and %d are supported", n_chunks, kChunkMax);
+    if (!chunks || !chunk_rows) return fail(VC2_ERR_ARG, "null pointer");
+    int64_t sum = 0;
+    for (int c = 0; c < n_chunks; ++c) {
+      if (!chunks[c] || chunk_rows[c] < 1) return fail(VC2_ERR_ARG, "chunk %d: null pointer or no rows", c);
+      sum += chunk_rows[c];
+    }
+    if (sum != F_total * N)
+      return fail(VC2_ERR_ARG, "the chunks hold %lld rows, the video %lld", (long long)sum, (long long)(F_total * N));
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  float* scales = wsp<float>(sel_ws, w.o_scales);
+  // vc2_select_sharded's launches with f0 = 0 and F_local = F_total: budgets and selection over the whole video once
+  if (F_total <= kFusedScalesMaxF) {
+    rc = launch_select(at_of(so.pdt), total_f32, F_total, 0, F_total, N, VC2_MAP_LINEAR, 0, ks, wsp<int64_t>(sel_ws, w.o_offs),
+                       idx_out, cap, K_out, BudgetSrc{nullptr, nullptr, 0, s_all_f32, base_scale, so.ps.temp, nullptr}, st);
+  } else {
+    if ((rc = launch_scales(at_of(so.pdt), s_all_f32, F_total, base_scale, so.ps.temp, wsp<float>(sel_ws, w.o_zbuf), scales, nullptr, st)))
+      return rc;
+    rc = launch_select(at_of(so.pdt), total_f32, F_total, 0, F_total, N, VC2_MAP_LINEAR, 0, ks, wsp<int64_t>(sel_ws, w.o_offs),
+                       idx_out, cap, K_out, BudgetSrc{scales, nullptr, 0, nullptr, base_scale, so.ps.temp, nullptr}, st);
+  }
+  if (rc) return rc;
+  if (hipMemsetAsync(K_out + 2, 0, 8, st) != hipSuccess ||
+      hipMemcpyAsync(K_out + 2, wsp<int>(const_cast<void*>(stage_ws), p.o_ticket) + kTkVcFragile, 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    return fail(VC2_ERR_LAUNCH, "status copy failed");
+  if (out_rows)
+    rc = launch_gather_rows_chunks(chunks, chunk_rows, n_chunks, D, p.ES, idx_out, K_out, cap, out_rows, cap, status, st);
+  return rc;
+}
+int vc2_select_chunks(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t N, int64_t D,
+                      double base_scale, int dtype, void* sel_ws, size_t sel_ws_bytes, const void* stage_ws,
+                      size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
+                      int64_t* K_out, const void* const* chunks, const int64_t* chunk_rows, int n_chunks, void* out_rows,
+                      int32_t* status, void* stream) {
+  return vc2_select_chunks_o(total_f32, s_all_f32, F_total, N, D, base_scale, dtype, sel_ws, sel_ws_bytes, stage_ws, stage_ws_bytes, stage_frames, ks, idx_out, cap, K_out, chunks, chunk_rows, n_chunks, out_rows, status, stream, nullptr);
 }
 
 int vc2_multi_scale_gaussian(const void* x, int64_t F, int64_t N, int64_t C, int dtype, const void* centre,

@@ -114,14 +114,28 @@ class HipStages:
     """The five shard-local stages on the HIP kernels (include/vc2.h 'frame-sharded building blocks')."""
 
     def __init__(self, F: int, N: int, D: int, dtype, device, base_scale: float, gather: bool = True,
-                 vc_cap: int = 64, frames=None, rank: int = 0, params=None, score_dtype=None):
+                 vc_cap: int = 64, frames=None, rank: int = 0, params=None, score_dtype=None, shared=None):
         """frames / rank: the layout of the video over the ranks (every rank's frame count, this rank's number).  None,
         or equal counts: the equal-shard pass (F_total = world * F, set by ShardedCompressor).  Unequal counts: the buffers
         that take part in an exchange are sized for the largest rank and exchange 2b goes through the ragged entry points.
         params (a PassParams) / score_dtype: as in `compress`.  None, a set equal to the reference's defaults and
         score_dtype == dtype are the plain pass: the same entry points with the same arguments.  Bad sets raise here, as
-        CompressPlan raises them (ValueError / NotImplementedError), before any collective."""
+        CompressPlan raises them (ValueError / NotImplementedError), before any collective.
+        shared: externally owned buffers by attribute name (stats, csum, blocks, total, s, var_f32, mask, cols, perm, spos), each
+        of the shape and dtype this object would allocate: the stage then writes its partials there instead of into
+        buffers of its own (chunked.py hands over views of whole-video buffers, so that its "exchanges" copy nothing).
+        None: every buffer is allocated here, as it always was."""
         from .vidcom2 import _c_params, _norm_params, _norm_score_dtype
+        ext = dict(shared or {})
+
+        def buf(name, shape, dt, zero=False):
+            t = ext.pop(name, None)
+            if t is None:
+                return (torch.zeros if zero else torch.empty)(shape, dtype=dt, device=self.device)
+            if tuple(t.shape) != tuple(shape) or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"HipStages: shared buffer {name!r} must be a contiguous {dt} {tuple(shape)} tensor on "
+                                 f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            return t
         self.params = _norm_params(params)
         # fp32 scoring of bf16 / fp16 rows: 16-bit loads, fp32 variances, scores and selection; no "torch order" replay
         self.score32 = _norm_score_dtype(score_dtype, dtype) is not None
@@ -141,26 +155,29 @@ class HipStages:
         # the unsharded pass's blocks and every world size reduces to the same bits); unequal shards: the largest
         # power of two that divides every rank's count
         self.bf = stat_block_frames(self.frames if self.ragged else [F])
-        self.stats = torch.empty((F // self.bf, 2, D), dtype=torch.float64, device=self.device)
+        self.stats = buf("stats", (F // self.bf, 2, D), torch.float64)
         self.C = int(self._cparams.channels) if self._cparams is not None else int(D * 0.5)   # int(x.shape[-1] * ratio), vidcom2.py:41
         # exchange 2: per group of 16 frames the sums of x^ and, behind them, the groups' bounds of sum |x^|.  Unequal
         # shards: k_video_centre reads every rank's message as [half sums | half bounds], so a rank with fewer groups
         # than the largest pads INSIDE each half (zero rows: they change neither the sums nor the bounds)
         G = (F + 15) // 16
         self._G, self._Gmax = G, max((f + 15) // 16 for f in self.frames) if self.ragged else G
-        self.csum = torch.zeros((2 * self._Gmax, self.C), dtype=torch.float64, device=self.device)
+        self.csum = buf("csum", (2 * self._Gmax, self.C), torch.float64, zero=True)     # (a shared one: zeroed by its owner)
         self._csum_raw = (torch.empty((2 * G, self.C), dtype=torch.float64, device=self.device)
                           if G != self._Gmax else self.csum)
         self.F_total = sum(self.frames) if self.ragged else F   # equal shards: set by ShardedCompressor (world * F)
         # the layout as the ragged entry points take it: a host array of the ranks' row counts
         self._rank_rows = (ctypes.c_int64 * len(self.frames))(*[f * N for f in self.frames]) if self.ragged else None
-        self.var_f32 = torch.empty(D, dtype=torch.float32, device=self.device)
-        self.mask = torch.empty(D, dtype=torch.uint8, device=self.device)
-        self.cols = torch.empty(D, dtype=torch.int32, device=self.device)
-        self.perm = torch.empty(D, dtype=torch.int32, device=self.device)     # channels as nth_element left them
-        self.spos = torch.empty(D, dtype=torch.int32, device=self.device)     # their positions in that order
-        self.total = torch.empty(F * N, dtype=torch.float32, device=self.device)
-        self.s = torch.empty(F, dtype=torch.float32, device=self.device)
+        self.var_f32 = buf("var_f32", (D,), torch.float32)
+        self.mask = buf("mask", (D,), torch.uint8)
+        self.cols = buf("cols", (D,), torch.int32)
+        self.perm = buf("perm", (D,), torch.int32)                            # channels as nth_element left them
+        self.spos = buf("spos", (D,), torch.int32)                            # their positions in that order
+        # phase 1 replays torch.topk's channel ORDER (perm -> spos) in a rider workgroup of sweep 2.  Stages that share one
+        # spos (chunked.py) need it once: the others are told that spos is valid already (perm == NULL, include/vc2.h)
+        self.order_rider = True
+        self.total = buf("total", (F * N,), torch.float32)
+        self.s = buf("s", (F,), torch.float32)
         # a rank can hold the globally dominant frame: sum of its scales <= base * (F_local + 1)
         self.cap = min(F * N, int(L.vc2_kept_capacity(F + 1, N, base_scale)))
         self.idx = torch.empty(self.cap, dtype=torch.int64, device=self.device)
@@ -175,14 +192,16 @@ class HipStages:
         # four sums per complete run; then every column of the pass, plain ones included, is exchanged in it
         self.vc_tail = self.vc_replay and tail_columns(self.C) > 0
         self.vc_edge = VC_EDGE_TAIL if self.vc_tail else VC_EDGE
-        self.blocks = torch.zeros((self.vc_cap, 2 * self.vc_edge + 1 + (max(self.frames) if self.ragged else F) * N // 16),
-                                  dtype=torch.float32, device=self.device)
+        self.blocks = buf("blocks", (self.vc_cap, 2 * self.vc_edge + 1 + (max(self.frames) if self.ragged else F) * N // 16),
+                          torch.float32, zero=True)
         # the options of the `_o` entry points; None: the plain symbols, today's calls
         self._opts = None
         if self._cparams is not None or self.vc_tail or self.score32:
             self._opts = _CShardOpts(ctypes.addressof(self._cparams) if self._cparams is not None else None,
                                      DTYPE_CODE[torch.float32] if self.score32 else self.code, 1 if self.vc_tail else 0)
         self.rows = torch.empty((self.cap, D), dtype=dtype, device=self.device) if gather else None
+        if ext:
+            raise ValueError(f"HipStages: unknown shared buffer(s) {sorted(ext)}")
 
         # device pointers of the fixed buffers, resolved once: the per-pass host work is five C calls plus
         # three collectives, and that host time bounds the pass when it exceeds the ~0.3 ms of GPU work
@@ -229,7 +248,8 @@ class HipStages:
     def phase1(self, x):
         p = self._p
         self._call("vc2_scores_phase1", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
-                   p["perm"], p["var_f32"], self.F_total, p["ws"], self._ws_n, p["_csum_raw"], self._st())
+                   p["perm"] if self.order_rider else None, p["var_f32"], self.F_total, p["ws"], self._ws_n,
+                   p["_csum_raw"], self._st())
         if self._G != self._Gmax:                               # fewer groups than the largest rank: pad inside each half
             self.csum[: self._G].copy_(self._csum_raw[: self._G])
             self.csum[self._Gmax: self._Gmax + self._G].copy_(self._csum_raw[self._G:])
