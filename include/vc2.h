@@ -86,7 +86,21 @@ const char* vc2_version(void);
 int vc2_set_mode(int mode);
 int vc2_set_thread_mode(int mode);
 int vc2_get_mode(void);
-/* Workspace (bytes) needed by any entry point below for an [F*N, D] input. */
+/* Workspace (bytes) needed by any entry point below for an [F*N, D] input.
+ *   - ONE size per (F, N, D, dtype): the numerics mode (process-wide or a thread's override) does not change it, so a
+ *     workspace sized in one mode serves a pass issued in any other.  That one size also serves every variant of the pass:
+ *     any vc2_pass_params, either score_dtype, every flag, both mappings and the frame-sharded options need the same
+ *     layout or a smaller one (the whole video's frame count only lowers the number of sweep-1 row groups; fp32 scoring
+ *     drops the replay engine's arrays).
+ *   - Its CONTENTS ON ENTRY ARE IGNORED: uninitialised memory, another shape's leftovers, any bytes.  Every counter, status
+ *     word, queue, mark, sentinel and list the kernels keep there is re-armed by the call itself before its first reader
+ *     (DESIGN.md "Workspace regions: who writes before whom").  The one exception is what a call is TOLD to find there:
+ *     sweep 1's partials under VC2_FLAG_HAVE_STATS (left by vc2_pool_stats), and, between the calls of ONE frame-sharded
+ *     pass on one workspace, what its earlier calls left (vc2_chan_stats -> vc2_scores_phase1 -> vc2_video_centre_* ->
+ *     vc2_scores_phase2* -> vc2_select_sharded).
+ *   - A call writes only inside [ws, ws + vc2_workspace_bytes) and inside the stated extents of its outputs; with ws_bytes
+ *     below the size it returns VC2_ERR_WORKSPACE and enqueues nothing.
+ *   - The workspace belongs to the pass until the pass has finished on its stream: two passes in flight need two. */
 int vc2_workspace_bytes(int64_t F, int64_t N, int64_t D, int dtype, size_t* out_bytes);
 
 /* Upper bound on the number of kept tokens sum(ks) for a given base_scale: lets the caller

@@ -4845,7 +4845,12 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
   // workgroup lives for the whole sweep.  The ORDER riders ("torch order" mode, 16-bit inputs) are workgroups of the
   // same launch, so the splits are chosen to leave them slots -- with 512 + 16 workgroups the last 16 start when the
   // riders end and the sweep takes 51 instead of 36 us; with 384 + 16 it takes 41.
-  const int64_t riders = (cur_mode() && at_of(dt) != VC2_F32) ? rider_parts_max(p->R, D * p->ES) : 0;
+  const int64_t ord_riders = at_of(dt) != VC2_F32 ? rider_parts_max(p->R, D * p->ES) : 0;   // what a "torch order" mode attaches
+  const int64_t riders = cur_mode() ? ord_riders : 0;
+  // does dtype / shape take the ORD form of sweep 2 in a "torch order" mode?  16-bit arithmetic, the streamlined sweep's
+  // widths, frames of <= 512 tokens, at least one workgroup per frame resident next to the riders.  ONE predicate: it
+  // decides ord_m (with the mode) and the reservation of o_bsum (without it)
+  const bool ord_shape = at_of(dt) != VC2_F32 && (D == 1024 || D == 3584 || D == 4096) && N <= 512 && (512 - ord_riders) / F >= 1;
   // S is chosen from THIS rank's frames (occupancy), not from the whole video's: the frame sums are fp64 sums of
   // T-rounded x^ in [-1, 1] -- exact (so independent of how the rows are cut) for fp16 by range (2^-24 .. 1, <= 8192
   // rows: 48 bits), and for bf16 unless a nonzero |x^| < 2^-39 meets a frame sum > 2^6
@@ -4864,16 +4869,14 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
     // shapes, every frame workgroup resident next to the riders.  S - 1 workgroups for the first nA frames, S for the
     // others, as many as the slots allow (a workgroup needs at least one block; `part` holds 8 pieces per frame)
     p->ord_S = p->ord_m = p->ord_nA = 0;
-    if (cur_mode() != 0 && at_of(dt) != VC2_F32 && (D == 1024 || D == 3584 || D == 4096) && N <= 512) {
+    if (cur_mode() != 0 && ord_shape) {             // (a "torch order" mode on 16-bit arithmetic: `riders` is ord_riders)
       const int64_t nblk = std::max<int64_t>(1, N / 16);
       const int64_t smax = std::min<int64_t>(8, nblk), slots = 512 - riders;
-      const int64_t s_lo = std::min<int64_t>(smax, slots / F);
-      if (s_lo >= 1) {
-        const int64_t more = s_lo < smax ? std::min<int64_t>(F, slots - F * s_lo) : 0;     // frames that take s_lo + 1
-        if (more > 0) { p->ord_S = int(s_lo + 1); p->ord_nA = int(F - more); }
-        else { p->ord_S = int(s_lo); p->ord_nA = 0; }
-        p->ord_m = 1;
-      }
+      const int64_t s_lo = std::min<int64_t>(smax, slots / F);                              // >= 1: ord_shape
+      const int64_t more = s_lo < smax ? std::min<int64_t>(F, slots - F * s_lo) : 0;     // frames that take s_lo + 1
+      if (more > 0) { p->ord_S = int(s_lo + 1); p->ord_nA = int(F - more); }
+      else { p->ord_S = int(s_lo); p->ord_nA = 0; }
+      p->ord_m = 1;
     }
   }
   {
@@ -4903,7 +4906,7 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
   p->o_spos = take(size_t(D) * 4);
   p->o_perm = take(size_t(D) * 4);
   p->o_den = take(size_t(p->R) * 4);
-  p->o_part_col = take(size_t(F) * 8 * D * 8);                // (S <= 8 whatever the mode: one workspace size per shape)
+  p->o_part_col = take(size_t(F) * 8 * D * 8);                // (S <= 8 whatever the mode: one workspace size per shape, as o_bsum below)
   p->o_fc = take(size_t(F) * D * 4);
   p->o_csum = take(size_t(D) * 8);
   p->o_csum_part = take(size_t(2) * size_t(cdiv(F, kCentreFL)) * D * 8);   // [sums | bounds of sum |x^|][groups][C]
@@ -4928,7 +4931,9 @@ int make_plan(int64_t F, int64_t N, int64_t D, int dt, Plan* p, int64_t F_total 
   p->o_vticket = take(size_t(D) * 4);
   p->o_dmin = take(size_t(F) * 4);                 // per frame: the smallest denominator (centre-mean margins)
   p->o_tmp_f32 = take(size_t(std::max<int64_t>(p->R, D)) * 4);
-  p->o_bsum = take(p->ord_m > 0 ? size_t(F) * size_t(N / 16 + 1) * size_t(D / 2) * 4 : 0);   // (ORD) frame block sums, fp32
+  // (ORD) frame block sums, fp32: reserved for every ord_shape, whatever cur_mode() says now (ord_m, which decides the
+  // FORM, follows the mode) -- one workspace size per shape: a caller who sized it in one mode can run the pass in another
+  p->o_bsum = take(ord_shape ? size_t(F) * size_t(N / 16 + 1) * size_t(D / 2) * 4 : 0);
   p->o_rlist = take(size_t(2) * F * D * 4);        // frame means to replay: frame * C + column (k_frame_centres / fix riders -> frame_replay_wave)
   p->total_bytes = o;
   return VC2_OK;
