@@ -198,6 +198,22 @@ int vc2_gather_rows_chunks(const void* const* chunks /* host [n_chunks] device p
                            const int64_t* idx, const int64_t* n_dev, int64_t n_max, void* dst, int64_t dst_rows,
                            int32_t* status, void* stream);
 
+/* vidcom2.py:89-91, :93-96, :105-115 (the reference's models/llava.py:118-127)  vc2_gather_rows_chunks with the options
+ * of the one-shot pass's gather.  h == 0: idx[] holds rows of the virtual concatenation, as there.  h > 0: idx[] holds
+ * slots g = f*h*(h+1) + r*(h+1) + c of the [F_total*h*(h+1), D] stream add_token_per_grid would build over the virtual
+ * concatenation (F_total = sum chunk_rows / (h*h)); dst[j,:] is the [D] vector `newline` for c == h and row
+ * f*h*h + r*h + c of the concatenation otherwise -- neither the concatenation nor the stream is built.  In both spaces
+ * `tail_rows` rows of `tail` are written behind row n = min(n_dev[0], n_max) (n_dev NULL: n_max).  An index outside its
+ * space, or a destination row >= dst_rows, is skipped -- never read or written -- and reported: *status |= 2.  Chunk
+ * bases, newline and tail of any alignment.  Codes as vc2_gather_rows_chunks, and VC2_ERR_ARG for h < 0, h > 0 with a
+ * null newline or with a chunk_rows entry that is not a multiple of h*h, tail_rows < 0, tail_rows > 0 with a null tail;
+ * nothing is enqueued. */
+int vc2_gather_rows_grid_chunks(const void* const* chunks /* host [n_chunks] device pointers */,
+                                const int64_t* chunk_rows /* host [n_chunks] */, int n_chunks, int64_t h, int64_t D,
+                                int dtype, const int64_t* idx, const int64_t* n_dev, int64_t n_max, const void* newline,
+                                const void* tail, int64_t tail_rows, void* dst, int64_t dst_rows, int32_t* status,
+                                void* stream);
+
 /* ---- one-shot hot path -------------------------------------------------------------- */
 
 /* vidcom2.py:15-36  vidcom2_compression for the "linear" mapper (llava_ov / qwen*), and for
@@ -650,6 +666,29 @@ int vc2_select_chunks_o(const float* total_f32, const float* s_all_f32, int64_t 
                         size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
                         int64_t* K_out, const void* const* chunks /* host */, const int64_t* chunk_rows /* host */,
                         int n_chunks, void* out_rows, int32_t* status, void* stream, const vc2_shard_opts* opts);
+/* vidcom2.py:70-78, :89-96, :105-115  vc2_select_chunks_o with the mapping and gather options of vc2_compress_ex5.
+ * VC2_MAP_GRID_VID (grid_h * grid_h == N): idx_out is in the slot space of the [F_total*grid_h*(grid_h+1), D] stream,
+ * every frame's kept tokens are followed by its grid_h newline slots and K_out[0] counts them; `cap` is then the
+ * unsharded pass's capacity plus F_total * grid_h.  out_rows is [cap + tail_rows, D] and is written by
+ * vc2_gather_rows_grid_chunks' kernel: kept rows from the chunk table, newline slots from `newline`, `tail_rows` rows of
+ * `tail` behind row K.  VC2_ERR_ARG: another map mode, grid_h * grid_h != N under the grid mode, a newline without the grid
+ * mode, the grid mode with out_rows but no newline, tail_rows < 0 or without tail; nothing is enqueued.  VC2_MAP_LINEAR
+ * without newline and tail: vc2_select_chunks_o (which forwards here), its launches and its bits. */
+int vc2_select_chunks_x(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t N, int64_t D,
+                        double base_scale, int dtype, void* sel_ws, size_t sel_ws_bytes, const void* stage_ws,
+                        size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
+                        int64_t* K_out, const void* const* chunks /* host */, const int64_t* chunk_rows /* host */,
+                        int n_chunks, void* out_rows, int32_t* status, void* stream, const vc2_shard_opts* opts,
+                        int map_mode, int64_t grid_h, const void* newline, const void* tail, int64_t tail_rows);
+
+/* llava_arch.py:171-190 + vidcom2.py:39-40 for ONE chunk of a frame-sharded / chunked video: vc2_pool_stats with the plan
+ * of vc2_chan_stats_o (F_total frames in the whole video, stat blocks of block_frames frames), followed by the block
+ * reduction vc2_chan_stats_o runs: x_out = the pooled chunk, bstats[F / block_frames, 2, D] = what
+ * vc2_chan_stats_o(x_out, F, h*w, D, ...) would write -- the chunk's sweep 1 never runs.  ws: the chunk's stage workspace.
+ * Limits and codes of vc2_pool_stats and vc2_chan_stats_o; opts as there (NULL: the plain pass). */
+int vc2_pool_stats_blocks(const void* xin, int64_t F, int64_t H, int64_t W, int64_t D, int dtype, int mode,
+                          int64_t F_total, int block_frames, void* ws, size_t ws_bytes, void* x_out, double* bstats,
+                          void* stream, const vc2_shard_opts* opts);
 
 /* _multi_scale_gaussian(x, center, alphas) as a standalone call -- vidcom2.py:59-62 (the fused pass
  * never materialises x; this entry serves callers of the helper itself).  x: T[F*N, C] as given,

@@ -37,6 +37,7 @@ _SIGNATURES = {
     "vc2_gather_rows": [_vp, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp],
     "vc2_gather_rows_grid": [_vp, _i64, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp],
     "vc2_gather_rows_chunks": [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
+    "vc2_gather_rows_grid_chunks": [_vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
     "vc2_compress": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
                      _vp, _vp, _vp, _vp],
     "vc2_compress_ex": [_vp, _i64, _i64, _i64, _i32, _dbl, _i32, _i64, _vp, _i64, _vp, _sz, _vp, _vp, _i64, _vp,
@@ -52,6 +53,7 @@ _SIGNATURES = {
     "vc2_wait_host_count": [_vp, _dbl],
     "vc2_pool_out_tokens": [_i64, _i64, _i32, _vp, _vp],
     "vc2_pool_stats": [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp],
+    "vc2_pool_stats_blocks": [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _i64, _i32, _vp, _sz, _vp, _vp, _vp, _vp],
     "vc2_gather_scatter": [_vp, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "vc2_keep_positions": [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp],
     "vc2_keep_positions_batched": [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64,
@@ -109,6 +111,9 @@ for _name in ("vc2_chan_stats", "vc2_scores_phase1", "vc2_video_centre_blocks", 
               "vc2_video_centre_blocks_round_ragged", "vc2_video_centre_finish_round_ragged",
               "vc2_scores_phase2_blocks_ragged", "vc2_select_sharded", "vc2_select_chunks"):
     _SIGNATURES[_name + "_o"] = _SIGNATURES[_name] + [_vp]
+
+# vc2_select_chunks_o and, behind the options: map_mode, grid_h, newline, tail, tail_rows
+_SIGNATURES["vc2_select_chunks_x"] = _SIGNATURES["vc2_select_chunks_o"] + [_i32, _i64, _vp, _vp, _i64]
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -4183,6 +4183,69 @@ __global__ __launch_bounds__(256) void k_gather_rows_chunks(ChunkGatherArgs a) {
   if ((blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && threadIdx.x == 0) VC2_STAMP(909);
 }
 
+// The chunked gather with the options of the one-shot pass's gather (vidcom2.py:91, :93-96, :105-115 for a video that
+// lies in several allocations; the reference's models/llava.py:118-127): the chunk table of k_gather_rows_chunks, the
+// slot space and the newline vector of k_gather_rows_grid, the tail rows of k_gather_rows.  h == 0: idx[] holds rows of
+// the virtual concatenation.  h > 0: idx[] holds slots g = f * h * (h + 1) + r * (h + 1) + c of the virtual
+// [F_total * h * (h + 1), D] stream over the virtual concatenation -- the newline vector for c == h, else row
+// f * h * h + r * h + c of the concatenation, whose owner the binary search finds.  The branch on h is uniform for the
+// launch, the search for the workgroup.  `space` (the rows of idx[]'s index space) is derived from the table on the host,
+// so that a slot inside it always decodes to a row inside the table.  Those three kernels stay as they are.
+struct GridChunkGatherArgs {
+  const unsigned char* src[kChunkMax];   // base of every chunk
+  int64_t start[kChunkMax + 1];          // start[c] = rows in front of chunk c; start[n_chunks] = rows of the video
+  const unsigned char* newline;          // [D] (h > 0)
+  const unsigned char* tail;             // rows appended behind the gathered ones (null: none)
+  unsigned char* dst;                    // [dst_rows, D]
+  int64_t space;                         // h == 0: start[n_chunks]; h > 0: start[n_chunks] / (h * h) * h * (h + 1)
+  int64_t dst_rows;
+  int64_t row_bytes;
+  const int64_t* idx;                    // [n] rows (h == 0) or slots (h > 0)
+  const int64_t* n_dev;                  // n on the device (null: n_max)
+  int64_t n_max;
+  int64_t tail_rows;
+  int* status;                           // null, or a device word: |= 2 for an index outside its space or a row past dst
+  int n_chunks;
+  int h;
+};
+__global__ __launch_bounds__(256) void k_gather_rows_grid_chunks(GridChunkGatherArgs a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) VC2_STAMP(900);
+  const int64_t n = a.n_dev ? min(a.n_dev[0], a.n_max) : a.n_max;
+  const int64_t total = n + a.tail_rows;
+  const int64_t h = a.h, w = h + 1;
+  for (int64_t j = blockIdx.x; j < total; j += gridDim.x) {
+    if (j >= a.dst_rows) { if (a.status && threadIdx.x == 0) atomicOr(a.status, 2); continue; }
+    unsigned char* const d = a.dst + j * a.row_bytes;
+    if (j >= n) {                                                // the tail rows, behind the last gathered one
+      copy_row(a.tail + (j - n) * a.row_bytes, d, a.row_bytes);
+      continue;
+    }
+    int64_t r = a.idx[j];
+    if (r < 0 || r >= a.space) { if (a.status && threadIdx.x == 0) atomicOr(a.status, 2); continue; }
+    if (h > 0) {                                                 // slot -> (frame, grid row, column)
+      int64_t f, gr, c;
+      if (a.space <= int64_t(0xffffffffu)) {                     // (every real shape: 32-bit divisions)
+        const uint32_t g32 = uint32_t(r), w32 = uint32_t(w), fw = uint32_t(h) * w32;
+        const uint32_t f32 = g32 / fw, rem = g32 - f32 * fw, r32 = rem / w32;
+        f = f32; gr = r32; c = rem - r32 * w32;
+      } else {
+        f = r / (h * w);
+        const int64_t rem = r - f * (h * w);
+        gr = rem / w; c = rem - gr * w;
+      }
+      if (c == h) { copy_row(a.newline, d, a.row_bytes); continue; }
+      r = (f * h + gr) * h + c;                                  // < start[n_chunks], as space was made from it
+    }
+    int lo = 0, hi = a.n_chunks;                                 // start[lo] <= r < start[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (r >= a.start[mid]) lo = mid; else hi = mid;
+    }
+    copy_row(a.src[lo] + (r - a.start[lo]) * a.row_bytes, d, a.row_bytes);
+  }
+  if ((blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && threadIdx.x == 0) VC2_STAMP(909);
+}
+
 // Sequence positions a pruned prefill keeps (hooks, reference models/qwen2_5_vl.py:153-160): every position that is
 // not a video token, plus the video tokens whose ordinal is in `kept` (ascending).  keep_out = those positions in
 // order; vis_rows_out (optional) = for the positions flagged in visual_mask, the ordinals (among them) that are
@@ -4950,12 +5013,14 @@ int check_launch(const char* what) {
 // ---- optional per-kernel timing (bench.py's roofline leg): hipEvents around every launch --------
 enum KernelId { KID_STATS = 0, KID_STATS_REDUCE, KID_CHAN_SELECT, KID_NORM_COLSUM, KID_CENTRES, KID_DIST,
                 KID_EPILOGUE, KID_SCALES, KID_KS, KID_SELECT, KID_GATHER_ROWS, KID_OTHER, KID_CHAN_ORDER, KID_DIST_FIX,
-                KID_CENTRE_FIX, KID_VC_RECORDS, KID_GATHER_ROWS_GRID, KID_GATHER_ROWS_CHUNKS, KID_COUNT };
+                KID_CENTRE_FIX, KID_VC_RECORDS, KID_GATHER_ROWS_GRID, KID_GATHER_ROWS_CHUNKS, KID_GATHER_ROWS_GRID_CHUNKS,
+                KID_COUNT };
 const char* const kKernelNames[KID_COUNT] = {"k_chan_stats", "k_stats_reduce", "k_chan_select", "k_norm_colsum",
                                              "k_centres", "k_dist", "k_token_epilogue", "k_scales", "k_ks(unused)",
                                              "k_select", "k_gather_rows", "k_norm_fix", "k_chan_order",
                                              "k_dist_fix", "k_centre_fix", "k_vc_records",
-                                             "k_gather_rows_grid", "k_gather_rows_chunks"};
+                                             "k_gather_rows_grid", "k_gather_rows_chunks",
+                                             "k_gather_rows_grid_chunks"};
 struct ProfRec { int id; hipEvent_t a, b; };
 bool g_prof = false;                // (bench-only; the record list is mutex-protected)
 std::mutex g_prof_mu;
@@ -5488,6 +5553,58 @@ int launch_gather_rows_chunks(const void* const* chunks, const int64_t* chunk_ro
   ProfScope ps_(KID_GATHER_ROWS_CHUNKS, st);
   hipLaunchKernelGGL(k_gather_rows_chunks, dim3(unsigned(std::min<int64_t>(n_max, 16384))), dim3(256), 0, st, a);
   return check_launch("gather_rows_chunks");
+}
+
+// the chunk table of the gather with options, checked: n_chunks, the pointers, the row counts (h > 0: whole h x h frames);
+// *rows = the rows of the video
+int check_chunk_table(const void* const* chunks, const int64_t* chunk_rows, int n_chunks, int64_t h, int64_t* rows) {
+  if (n_chunks < 1 || n_chunks > kChunkMax)
+    return fail(VC2_ERR_UNSUPPORTED, "%d chunks: between 1 and %d are supported", n_chunks, kChunkMax);
+  if (!chunks || !chunk_rows) return fail(VC2_ERR_ARG, "null pointer");
+  if (h < 0 || h > 32768) return fail(VC2_ERR_ARG, "grid height %lld: 0 (rows of the video) or 1..32768", (long long)h);
+  int64_t sum = 0;
+  for (int c = 0; c < n_chunks; ++c) {
+    if (!chunks[c]) return fail(VC2_ERR_ARG, "chunk %d: null pointer", c);
+    if (chunk_rows[c] < 1) return fail(VC2_ERR_ARG, "chunk %d holds %lld rows", c, (long long)chunk_rows[c]);
+    if (h > 0 && chunk_rows[c] % (h * h) != 0)
+      return fail(VC2_ERR_ARG, "chunk %d holds %lld rows: not whole frames of %lld x %lld tokens", c,
+                  (long long)chunk_rows[c], (long long)h, (long long)h);
+    sum += chunk_rows[c];
+  }
+  *rows = sum;
+  return VC2_OK;
+}
+// the chunked form with the grid's slot space, the newline vector and tail rows (k_gather_rows_grid_chunks).  Everything
+// is checked here: nothing is enqueued on a bad table or argument
+int launch_gather_rows_grid_chunks(const void* const* chunks, const int64_t* chunk_rows, int n_chunks, int64_t h, int64_t D,
+                                   int ES, const int64_t* idx, const int64_t* n_dev, int64_t n_max, const void* newline,
+                                   const void* tail, int64_t tail_rows, void* dst, int64_t dst_rows, int* status,
+                                   hipStream_t st) {
+  int64_t rows = 0;
+  int rc = check_chunk_table(chunks, chunk_rows, n_chunks, h, &rows);
+  if (rc) return rc;
+  if (!idx || !dst) return fail(VC2_ERR_ARG, "null pointer");
+  if (D <= 0 || n_max < 0 || dst_rows < 0) return fail(VC2_ERR_ARG, "bad gather_rows_grid_chunks arguments");
+  if (h > 0 && !newline) return fail(VC2_ERR_ARG, "a grid height without the newline vector");
+  if (tail_rows < 0 || (tail_rows > 0 && !tail)) return fail(VC2_ERR_ARG, "tail_rows without tail");
+  GridChunkGatherArgs a{};
+  a.start[0] = 0;
+  for (int c = 0; c < n_chunks; ++c) {
+    a.src[c] = static_cast<const unsigned char*>(chunks[c]);
+    a.start[c + 1] = a.start[c] + chunk_rows[c];
+  }
+  for (int c = n_chunks; c < kChunkMax; ++c) a.start[c + 1] = a.start[n_chunks];
+  a.newline = static_cast<const unsigned char*>(newline); a.tail = static_cast<const unsigned char*>(tail);
+  a.dst = static_cast<unsigned char*>(dst);
+  a.space = h > 0 ? rows / (h * h) * h * (h + 1) : rows;
+  a.dst_rows = dst_rows; a.row_bytes = D * ES;
+  a.idx = idx; a.n_dev = n_dev; a.n_max = n_max; a.tail_rows = tail ? tail_rows : 0;
+  a.status = status; a.n_chunks = n_chunks; a.h = int(h);
+  const int64_t out = a.n_max + a.tail_rows;
+  if (out <= 0) return VC2_OK;
+  ProfScope ps_(KID_GATHER_ROWS_GRID_CHUNKS, st);
+  hipLaunchKernelGGL(k_gather_rows_grid_chunks, dim3(unsigned(std::min<int64_t>(out, 16384))), dim3(256), 0, st, a);
+  return check_launch("gather_rows_grid_chunks");
 }
 
 #endif   // VC2_DEV_ONLY
@@ -6164,6 +6281,36 @@ int vc2_pool_stats(const void* xin, int64_t F, int64_t H, int64_t W, int64_t D, 
   return launch_stats_sweep(p, x_out, ws, pool, static_cast<hipStream_t>(stream));
 }
 
+// vc2_pool_stats for one chunk of a frame-sharded / chunked video: the plan of vc2_chan_stats_o (the whole video's frame
+// count cuts the sweep-1 groups, block_frames the stat blocks), the pooling sweep, then the block reduction
+// vc2_chan_stats_o runs on the partials -- bstats holds what vc2_chan_stats_o(x_out, ...) would write, x_out is read by
+// no sweep 1
+int vc2_pool_stats_blocks(const void* xin, int64_t F, int64_t H, int64_t W, int64_t D, int dtype, int mode,
+                          int64_t F_total, int block_frames, void* ws, size_t ws_bytes, void* x_out, double* bstats,
+                          void* stream, const vc2_shard_opts* opts) {
+  if (!xin || !x_out || !bstats) return fail(VC2_ERR_ARG, "null pointer");
+  int64_t h, w;
+  int rc = vc2_pool_out_tokens(H, W, mode, &h, &w);
+  if (rc) return rc;
+  if (H > 32768 || W > 32768) return fail(VC2_ERR_UNSUPPORTED, "H, W up to 32768");
+  if (mode == VC2_POOL_BILINEAR && D % (dtype == VC2_F32 ? 8 : 16) != 0)
+    return fail(VC2_ERR_UNSUPPORTED, "bilinear pooling: D=%lld is not a multiple of torch's vector width (%d)",
+                (long long)D, dtype == VC2_F32 ? 8 : 16);
+  if (mode == VC2_POOL_BILINEAR && h + w > 128)      // (see vc2_pool_stats)
+    return fail(VC2_ERR_UNSUPPORTED, "bilinear pooling to %lld x %lld: torch switches kernels (and summation order) "
+                "beyond out_h + out_w = 128", (long long)h, (long long)w);
+  if (block_frames < 1 || block_frames > kStatBlockFrames) return fail(VC2_ERR_ARG, "block_frames must be 1..%d", kStatBlockFrames);
+  ShardOpts so;
+  { int rco = shard_opts(opts, dtype, D, 0, &so); if (rco) return rco; }
+  Plan p;
+  if ((rc = make_plan(F, h * w, D, so.pdt, &p, F_total, block_frames, opts != nullptr))) return rc;
+  if ((rc = need_ws(p, ws, ws_bytes))) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const PoolSrc pool{xin, int(H), int(W), int(h), int(w), mode};
+  if ((rc = launch_stats_sweep(p, x_out, ws, pool, st))) return rc;
+  return launch_chan_stats(p, x_out, ws, bstats, nullptr, nullptr, st, /*zero_queue_counters=*/false, /*have_partials=*/true);
+}
+
 int vc2_gather_scatter(const void* const* srcs, const int64_t* src_rows, void* const* dsts, const int64_t* dst_rows,
                        int n_src, int64_t D, int dtype, const int64_t* idx, const int64_t* n_dev, int64_t n_max,
                        const int64_t* dst_pos, int64_t dst_row0, const void* tail, int64_t tail_rows, int32_t* status,
@@ -6339,6 +6486,17 @@ int vc2_gather_rows_chunks(const void* const* chunks, const int64_t* chunk_rows,
   if (dtype < VC2_F32 || dtype > VC2_F16) return fail(VC2_ERR_ARG, "unknown dtype code %d", dtype);
   return launch_gather_rows_chunks(chunks, chunk_rows, n_chunks, D, dtype == VC2_F32 ? 4 : 2, idx, n_dev, n_max, dst,
                                    dst_rows, status, static_cast<hipStream_t>(stream));
+}
+
+int vc2_gather_rows_grid_chunks(const void* const* chunks, const int64_t* chunk_rows, int n_chunks, int64_t h, int64_t D,
+                                int dtype, const int64_t* idx, const int64_t* n_dev, int64_t n_max, const void* newline,
+                                const void* tail, int64_t tail_rows, void* dst, int64_t dst_rows, int32_t* status,
+                                void* stream) {
+  if (n_chunks < 1 || n_chunks > kChunkMax)
+    return fail(VC2_ERR_UNSUPPORTED, "%d chunks: between 1 and %d are supported", n_chunks, kChunkMax);
+  if (dtype < VC2_F32 || dtype > VC2_F16) return fail(VC2_ERR_ARG, "unknown dtype code %d", dtype);
+  return launch_gather_rows_grid_chunks(chunks, chunk_rows, n_chunks, h, D, dtype == VC2_F32 ? 4 : 2, idx, n_dev, n_max,
+                                        newline, tail, tail_rows, dst, dst_rows, status, static_cast<hipStream_t>(stream));
 }
 
 int vc2_compress(const void* x, int64_t F, int64_t N, int64_t D, int dtype, double base_scale, int map_mode,
@@ -6590,11 +6748,38 @@ int vc2_select_chunks_o(const float* total_f32, const float* s_all_f32, int64_t 
                         size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
                         int64_t* K_out, const void* const* chunks, const int64_t* chunk_rows, int n_chunks, void* out_rows,
                         int32_t* status, void* stream, const vc2_shard_opts* opts) {
+  return vc2_select_chunks_x(total_f32, s_all_f32, F_total, N, D, base_scale, dtype, sel_ws, sel_ws_bytes, stage_ws, stage_ws_bytes, stage_frames, ks, idx_out, cap, K_out, chunks, chunk_rows, n_chunks, out_rows, status, stream, opts, VC2_MAP_LINEAR, 0, nullptr, nullptr, 0);
+}
+int vc2_select_chunks(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t N, int64_t D,
+                      double base_scale, int dtype, void* sel_ws, size_t sel_ws_bytes, const void* stage_ws,
+                      size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
+                      int64_t* K_out, const void* const* chunks, const int64_t* chunk_rows, int n_chunks, void* out_rows,
+                      int32_t* status, void* stream) {
+  return vc2_select_chunks_o(total_f32, s_all_f32, F_total, N, D, base_scale, dtype, sel_ws, sel_ws_bytes, stage_ws, stage_ws_bytes, stage_frames, ks, idx_out, cap, K_out, chunks, chunk_rows, n_chunks, out_rows, status, stream, nullptr);
+}
+
+// the mapping and the gather options of the one-shot pass (vc2_compress_ex5) on top of vc2_select_chunks_o, which forwards
+// here: the grid's slot space and newline vector, tail rows.  Without them the launches are the ones vc2_select_chunks_o
+// always made, k_gather_rows_chunks included
+int vc2_select_chunks_x(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t N, int64_t D,
+                        double base_scale, int dtype, void* sel_ws, size_t sel_ws_bytes, const void* stage_ws,
+                        size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
+                        int64_t* K_out, const void* const* chunks, const int64_t* chunk_rows, int n_chunks, void* out_rows,
+                        int32_t* status, void* stream, const vc2_shard_opts* opts, int map_mode, int64_t grid_h,
+                        const void* newline, const void* tail, int64_t tail_rows) {
   if (!total_f32 || !s_all_f32 || !ks || !idx_out || !K_out || !sel_ws || !stage_ws) return fail(VC2_ERR_ARG, "null pointer");
   if (F_total <= 0 || F_total > kMaxFramesTotal || stage_frames <= 0 || stage_frames > F_total || cap < 0)
     return fail(VC2_ERR_ARG, "bad frame counts (%lld of %lld) or capacity", (long long)stage_frames, (long long)F_total);
   if (N <= 0) return fail(VC2_ERR_ARG, "N must be positive");
   if (N > 8192) return fail(VC2_ERR_UNSUPPORTED, "N=%lld > 8192 tokens per frame", (long long)N);
+  if (map_mode != VC2_MAP_LINEAR && map_mode != VC2_MAP_GRID_VID)
+    return fail(VC2_ERR_ARG, "map_mode %d: the chunked selection maps linearly or to the grid", map_mode);
+  const bool grid = map_mode == VC2_MAP_GRID_VID;
+  if (grid && (grid_h <= 0 || grid_h * grid_h != N)) return fail(VC2_ERR_ARG, "grid_vid mapping needs N == grid_h^2");
+  if (newline && !grid)
+    return fail(VC2_ERR_ARG, "a newline vector needs the grid_vid mapping (map_mode %d)", map_mode);
+  if (grid && out_rows && !newline) return fail(VC2_ERR_ARG, "the grid_vid mapping gathers with the newline vector");
+  if (tail_rows < 0 || (tail_rows > 0 && !tail)) return fail(VC2_ERR_ARG, "tail_rows without tail");
   ShardOpts so;
   { int rco = shard_opts(opts, dtype, D, 0, &so); if (rco) return rco; }
   Plan p;                                   // the stage's workspace: only its count of fragile centre columns is read
@@ -6605,14 +6790,8 @@ int vc2_select_chunks_o(const float* total_f32, const float* s_all_f32, int64_t 
   if (sel_ws_bytes < w.total_bytes)
     return fail(VC2_ERR_WORKSPACE, "selection scratch too small: %zu < %zu bytes", sel_ws_bytes, w.total_bytes);
   if (out_rows) {                           // the chunk table must be this video's (checked before anything is enqueued)
-    if (n_chunks < 1 || n_chunks > kChunkMax)
-      return fail(VC2_ERR_UNSUPPORTED, "%d chunks: between 1 and %d are supported", n_chunks, kChunkMax);
-    if (!chunks || !chunk_rows) return fail(VC2_ERR_ARG, "null pointer");
     int64_t sum = 0;
-    for (int c = 0; c < n_chunks; ++c) {
-      if (!chunks[c] || chunk_rows[c] < 1) return fail(VC2_ERR_ARG, "chunk %d: null pointer or no rows", c);
-      sum += chunk_rows[c];
-    }
+    if ((rc = check_chunk_table(chunks, chunk_rows, n_chunks, grid ? grid_h : 0, &sum))) return rc;
     if (sum != F_total * N)
       return fail(VC2_ERR_ARG, "the chunks hold %lld rows, the video %lld", (long long)sum, (long long)(F_total * N));
   }
@@ -6620,28 +6799,25 @@ int vc2_select_chunks_o(const float* total_f32, const float* s_all_f32, int64_t 
   float* scales = wsp<float>(sel_ws, w.o_scales);
   // vc2_select_sharded's launches with f0 = 0 and F_local = F_total: budgets and selection over the whole video once
   if (F_total <= kFusedScalesMaxF) {
-    rc = launch_select(at_of(so.pdt), total_f32, F_total, 0, F_total, N, VC2_MAP_LINEAR, 0, ks, wsp<int64_t>(sel_ws, w.o_offs),
+    rc = launch_select(at_of(so.pdt), total_f32, F_total, 0, F_total, N, map_mode, grid_h, ks, wsp<int64_t>(sel_ws, w.o_offs),
                        idx_out, cap, K_out, BudgetSrc{nullptr, nullptr, 0, s_all_f32, base_scale, so.ps.temp, nullptr}, st);
   } else {
     if ((rc = launch_scales(at_of(so.pdt), s_all_f32, F_total, base_scale, so.ps.temp, wsp<float>(sel_ws, w.o_zbuf), scales, nullptr, st)))
       return rc;
-    rc = launch_select(at_of(so.pdt), total_f32, F_total, 0, F_total, N, VC2_MAP_LINEAR, 0, ks, wsp<int64_t>(sel_ws, w.o_offs),
+    rc = launch_select(at_of(so.pdt), total_f32, F_total, 0, F_total, N, map_mode, grid_h, ks, wsp<int64_t>(sel_ws, w.o_offs),
                        idx_out, cap, K_out, BudgetSrc{scales, nullptr, 0, nullptr, base_scale, so.ps.temp, nullptr}, st);
   }
   if (rc) return rc;
   if (hipMemsetAsync(K_out + 2, 0, 8, st) != hipSuccess ||
       hipMemcpyAsync(K_out + 2, wsp<int>(const_cast<void*>(stage_ws), p.o_ticket) + kTkVcFragile, 4, hipMemcpyDeviceToDevice, st) != hipSuccess)
     return fail(VC2_ERR_LAUNCH, "status copy failed");
-  if (out_rows)
+  const int64_t nt = tail ? tail_rows : 0;
+  if (out_rows && !grid && nt == 0)
     rc = launch_gather_rows_chunks(chunks, chunk_rows, n_chunks, D, p.ES, idx_out, K_out, cap, out_rows, cap, status, st);
+  else if (out_rows)
+    rc = launch_gather_rows_grid_chunks(chunks, chunk_rows, n_chunks, grid ? grid_h : 0, D, p.ES, idx_out, K_out, cap, newline,
+                                        tail, nt, out_rows, cap + nt, status, st);
   return rc;
-}
-int vc2_select_chunks(const float* total_f32, const float* s_all_f32, int64_t F_total, int64_t N, int64_t D,
-                      double base_scale, int dtype, void* sel_ws, size_t sel_ws_bytes, const void* stage_ws,
-                      size_t stage_ws_bytes, int64_t stage_frames, int64_t* ks, int64_t* idx_out, int64_t cap,
-                      int64_t* K_out, const void* const* chunks, const int64_t* chunk_rows, int n_chunks, void* out_rows,
-                      int32_t* status, void* stream) {
-  return vc2_select_chunks_o(total_f32, s_all_f32, F_total, N, D, base_scale, dtype, sel_ws, sel_ws_bytes, stage_ws, stage_ws_bytes, stage_frames, ks, idx_out, cap, K_out, chunks, chunk_rows, n_chunks, out_rows, status, stream, nullptr);
 }
 
 int vc2_multi_scale_gaussian(const void* x, int64_t F, int64_t N, int64_t C, int dtype, const void* centre,

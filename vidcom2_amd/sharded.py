@@ -124,6 +124,8 @@ class HipStages:
         shared: externally owned buffers by attribute name (stats, csum, blocks, total, s, var_f32, mask, cols, perm, spos), each
         of the shape and dtype this object would allocate: the stage then writes its partials there instead of into
         buffers of its own (chunked.py hands over views of whole-video buffers, so that its "exchanges" copy nothing).
+        Two more are optional and never allocated here: v, f ([F, N] in the dtype the pass scores in) -- sweep 3 then
+        also writes this rank's video / frame scores there (v_T / f_T of the phase-2 entry points).
         None: every buffer is allocated here, as it always was."""
         from .vidcom2 import _c_params, _norm_params, _norm_score_dtype
         ext = dict(shared or {})
@@ -178,6 +180,9 @@ class HipStages:
         self.order_rider = True
         self.total = buf("total", (F * N,), torch.float32)
         self.s = buf("s", (F,), torch.float32)
+        sdt = torch.float32 if self.score32 else dtype
+        self.v = buf("v", (F, N), sdt) if "v" in ext else None
+        self.f = buf("f", (F, N), sdt) if "f" in ext else None
         # a rank can hold the globally dominant frame: sum of its scales <= base * (F_local + 1)
         self.cap = min(F * N, int(L.vc2_kept_capacity(F + 1, N, base_scale)))
         self.idx = torch.empty(self.cap, dtype=torch.int64, device=self.device)
@@ -208,7 +213,7 @@ class HipStages:
         self._L = L
         self._p = {n: ptr(getattr(self, n)) for n in ("ws", "stats", "csum", "var_f32", "mask", "cols", "perm",
                                                      "spos", "total", "s", "idx", "ks", "kout", "rows", "blocks",
-                                                     "_csum_raw")}
+                                                     "_csum_raw", "v", "f")}
         self._ws_n = self.ws.numel()
 
     def _call(self, name: str, *args):
@@ -226,6 +231,18 @@ class HipStages:
         if [int(f) for f in frames] != self.frames or int(rank) != self.rank:
             raise ValueError(f"HipStages was built for the layout {self.frames} (rank {self.rank}), not {list(frames)} "
                              f"(rank {rank}): pass frames= and rank= to its constructor")
+
+    def set_score_views(self, v, f) -> None:
+        """Other tensors for this rank's scores from the next phase 2 on (chunked.py: fresh ones per video), each a
+        contiguous [F, N] tensor in the dtype the pass scores in; None, None: no score outputs."""
+        sdt = torch.float32 if self.score32 else self.dtype
+        for name, t in (("v", v), ("f", f)):
+            if t is not None and (tuple(t.shape) != (self.F, self.N) or t.dtype != sdt or t.device != self.device
+                                  or not t.is_contiguous()):
+                raise ValueError(f"HipStages: score view {name!r} must be a contiguous {sdt} {(self.F, self.N)} tensor on "
+                                 f"{self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+            setattr(self, name, t)
+            self._p[name] = ptr(t)
 
     def chan_stats(self, x):
         p = self._p
@@ -323,12 +340,13 @@ class HipStages:
         if self.ragged and blocks_all is not None:
             self._call("vc2_scores_phase2_blocks_ragged", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C,
                        p["spos"], ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total, self._rank_rows,
-                       len(self.frames), self.rank, p["ws"], self._ws_n, None, None, p["total"], p["s"], ptr(blocks_all),
+                       len(self.frames), self.rank, p["ws"], self._ws_n, p["v"], p["f"], p["total"], p["s"], ptr(blocks_all),
                        self.vc_cap, self._st())
             return self.s
         self._call("vc2_scores_phase2_blocks", ptr(x), self.F, self.N, self.D, self.code, p["cols"], self.C, p["spos"],
-                   ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total, p["ws"], self._ws_n, None, None,
-                   p["total"], p["s"], ptr(blocks_all) if blocks_all is not None else None, world, self.vc_cap, self._st())
+                   ptr(parts), parts.shape[0], parts.shape[1], self.csum.shape[0], R_total, p["ws"], self._ws_n, p["v"],
+                   p["f"], p["total"], p["s"], ptr(blocks_all) if blocks_all is not None else None, world, self.vc_cap,
+                   self._st())
         return self.s
 
     def select(self, x, s_all, f0):
